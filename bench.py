@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the batched Opus frame path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--workload celt|celt_streams|mdct|silk|silk_deldec|decode|mixed] [--frames F]
 
-One "step" = one pass of the hot path over one batch of synthetic frames already resident in HBM.
+One "step" = one pass of the hot path over one batch of synthetic frames already resident in HBM. A plain run sets up, runs
+the W warm-up steps, times the K steps and prints the result line. --full adds what takes runs of its own after the clock has
+stopped: the CPU baseline and the comparison of the last step with the reference. --dump-outputs DIR writes what the last
+timed step returned (packets, lengths, final ranges for the CELT encoder) as DIR/<name>.npy, float32 or float64, a fixed
+seeded sample of the rows where an array is large; the inputs are seeded, so two builds can be compared file by file.
 
   celt (default)  BASELINE.json configs[2]: 65 536 independent 48 kHz stereo 20 ms frames per GPU (each the first frame
                   of its own stream), full CELT encode (opus_encode(): dc_reject, pre-emphasis, pitch pre-filter, MDCT,
@@ -47,9 +51,9 @@ overlapping the encode of step k+1), so scaling is "weak" and `value` is the who
 differs from --gpus is an error.
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant kernel, timed with HIP events
-on the launch stream), `cpu_baseline` (the reference's own C code timed on this box's host cores over a bounded
-sample) and `parity_checked` (units of the LAST timed step compared bit-exactly with the reference after the clock
-stopped; a mismatch is a failure, not a number).
+on the launch stream inside the timed steps) and, with --full, `cpu_baseline` (the reference's own C code timed on the
+host cores over a bounded sample) and `parity_checked` (units of the LAST timed step compared bit-exactly with the
+reference after the clock stopped; a mismatch is a failure, not a number; 0 in a plain run).
 
 --rehearse: no GPU and no codec work -- the ranks only rendezvous on gloo and run the packet gather on synthetic
 slabs; `value` is null. It exists so the multi-rank launch path can be tested on a CPU-only machine.
@@ -86,8 +90,12 @@ def parse(argv=None):
     ap.add_argument("--frames", type=int, default=None, help="frames (units) per GPU per step")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("CONCENTUS_BENCH_STREAMS", "1")),
                     help="celt: HIP streams the consecutive batches (steps) alternate over (each with its own workspace)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the post-clock comparison with the reference")
+    ap.add_argument("--full", action="store_true",
+                    help="after the clock also time the CPU baseline and compare the last step with the reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the post-clock comparison with the reference")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL packet gather (N > 1)")
     ap.add_argument("--rehearse", action="store_true", help="CPU only: rendezvous on gloo + packet gather, no codec work")
     return ap.parse_args(argv)
@@ -157,6 +165,41 @@ def check_packets(what, got_pk, got_len, got_rng, exp_pk, exp_len, exp_rng):
     mask = np.arange(w)[None, :] < exp_len[:, None]
     if not np.array_equal(np.where(mask, got_pk[:, :w], 0), np.where(mask, exp_pk[:, :w], 0)):
         raise SystemExit("PARITY FAILURE (%s): packet bytes differ" % what)
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------------------------------
+DUMP_BUDGET = 60 * 1000 * 1000     # bytes of array data over all files of one dump (the limit is 64 MB)
+
+
+def masked_packets(out, lens):
+    """The packet rows cut to the longest packet, with the bytes behind each packet's own length set to zero (only the first
+    lens[i] bytes of row i are the result)."""
+    import torch
+    w = max(1, min(int(lens.max().item()), out.shape[1]))
+    return out[:, :w] * (torch.arange(w, device=out.device)[None, :] < lens[:, None]).to(out.dtype)
+
+
+def dump_outputs(dirname, arrays):
+    """Write the arrays the last timed step returned as <dirname>/<name>.npy. Every output is an integer array: bytes and 16-bit
+    values are stored as float32, 32-bit values as float64 (both exact). An output that does not fit its share of the budget keeps
+    a sample of its rows, drawn with a fixed seed and kept in order, so that two runs with the same arguments store the same rows."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def stored_bytes(arr):
+        return arr.numel() * (4 if arr.element_size() <= 2 else 8)
+    left = DUMP_BUDGET
+    todo = sorted(arrays.items(), key=lambda kv: stored_bytes(kv[1]))      # small outputs first: what they leave goes to the large ones
+    for i, (name, arr) in enumerate(todo):
+        ft = np.float32 if arr.element_size() <= 2 else np.float64
+        share = left // (len(todo) - i)
+        n = arr.shape[0]
+        if stored_bytes(arr) > share:
+            row_bytes = max(stored_bytes(arr) // n, 1)
+            keep = np.sort(np.random.default_rng(20260401).choice(n, size=max(share // row_bytes, 1), replace=False))
+            arr = arr[torch.from_numpy(keep).to(arr.device)]
+        left -= stored_bytes(arr)
+        np.save(os.path.join(dirname, name + ".npy"), arr.cpu().numpy().astype(ft))
 
 
 # ---- CPU baselines (the checker's code timed on the host; never on the product path) ----------------------------
@@ -570,7 +613,16 @@ def main(argv=None):
     traffic_db = load_db("traffic.json")
     pmc_db = load_db("pmc.json")           # per kernel: wave-instructions per launch at the default batch (tools/pmc_db.py)
     sample_threads = host_threads()
-    parity = {"checked": 0, "note": "skipped (--no-parity)" if a.no_parity else ""}
+    # a plain run times the steps and nothing else: the CPU baseline and the comparison with the reference belong to --full
+    a.no_cpu_baseline = a.no_cpu_baseline or not a.full
+    a.no_parity = a.no_parity or not a.full
+    parity = {"checked": 0, "note": ("skipped (--no-parity)" if a.full else "not checked (plain run; --full checks)") if a.no_parity else ""}
+
+    def dump(arrays):
+        # called right after the timed region, before anything else runs the kernels again; `arrays` builds the dict on demand
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, arrays())
+
     limiter = "hbm"
     unit_bytes = None                      # SURVEY 8d algorithmic bytes per unit of the workload
 
@@ -598,6 +650,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"freq": freq, "rec": rec})
         fwd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         bwd_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
         if fwd_ms >= bwd_ms:
@@ -652,6 +705,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"pcm": pcm, "ret": ret, "final_range": dec.final_range})
         assert (ret.cpu().numpy() == 960).all(), "decoder reported an error"
         NK = 10
         ksum = (C.c_double * NK)()
@@ -722,6 +776,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"dd_out": do, "dd_state": st})
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_nsq_del_dec_kernel"
         kbytes = F * (1648 + 2 * 4380 + 324)
@@ -765,6 +820,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"lpc_out": lo[:, :36]})
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_find_lpc_kernel"
         kbytes = F * (832 + 40)
@@ -832,6 +888,8 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: dict({k: res[k][:, :nb] for k, nb in (("pitch_out", 1380), ("shape_out", 380), ("fpc_out", 204), ("gains_out", 52), ("prefilter_out", 1280))},
+                  pulses=res["pulses"], Seed=res["Seed"], nsq_state=nsq_st, prefilter_state=pf_st, ec_state=ec_st))
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_nsq_del_dec_kernel"           # the longest of the step's kernels; avg_launch_ms below is the WHOLE step (extra["note"])
         kbytes = F * (1408 + 324 + 4380 + 1116 + 1328)  # per frame: pitch buffer in, pulses + Seed out, the carried states and the coder rewritten
@@ -954,9 +1012,11 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"pulses": res["pulses"], "nsq_state": nsq_st, "prefilter_state": pf_st,
+              "ec_state_frame0": frames_dev[0]["ec"], "ec_state_frame1": frames_dev[-1]["ec"]})
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_nsq_del_dec_kernel"
-        kbytes = F * (640 + 324 + 1328)            # per frame: the samples in, pulses + Seed and the packet's coder out (the states stay on the device)
+        kbytes = F * (640 + 324 + 1328)           # per frame: the samples in, pulses + Seed and the packet's coder out (the states stay on the device)
         limiter = "latency / VALU issue (lane-per-frame kernels of serial fixed-point recurrences; whole two-frame step timed)"
         metric = "SILK 16kHz mono 20ms frames/sec, streams mode (silk_encode_frame_FIX incl. its bitrate loop, inter-frame state carried on the device)"
         workload = ("%d streams per GPU x %d consecutive frames per step (16 kHz mono synthetic speech, 32 kb/s VOIP CBR, complexity 5/7/10 in turn): the state "
@@ -1018,6 +1078,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: dict({ok: d_out[ok][:, :nb] for _, _, ok, nb, *_ in ANALYSIS_OPS}, prefilter_state=pf_st))
         per = [float(np.mean([e[j].elapsed_time(e[j + 1]) for e in ev])) for j in range(len(ANALYSIS_OPS))]
         kern = [{"kernel": ANALYSIS_OPS[j][6], "avg_launch_ms": round(per[j], 4),
                  "bytes_per_record": int(rec[ANALYSIS_OPS[j][1]].shape[1] + rec[ANALYSIS_OPS[j][2]].shape[1])} for j in range(len(ANALYSIS_OPS))]
@@ -1063,6 +1124,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"fpc_out": fo[:, :204]})
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_find_pred_coefs_kernel"
         kbytes = F * (2688 + 208)
@@ -1106,6 +1168,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"nlsf_out": no[:, :116], "resnrg_out": eo[:, :32]})
         kms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kname = "silk_process_nlsfs_kernel"
         kbytes = F * (96 + 120)
@@ -1148,6 +1211,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+        dump(lambda: {"burg_out": bo, "pulses": pulses, "nsq_state": st})
         burg_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         kms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
         kname = "silk_nsq_kernel"
@@ -1194,6 +1258,7 @@ def main(argv=None):
         elapsed = time.perf_counter() - t0
         barrier()
         _r = enc.final_range
+        dump(lambda: {"packets": masked_packets(out, lens), "lengths": lens, "final_range": _r})
         kern, mean_len = celt_kernel_table(ca, L, F, steps, lens, traffic_db)
         dom = kern[0]
         kname, kms = dom["kernel"], dom["avg_launch_ms"]
@@ -1307,6 +1372,8 @@ def main(argv=None):
         barrier()
         if gathered and gathered[0] is not None and gather_w and truncated(gathered[0][1], pending[0].width):
             raise SystemExit("packet gather: a packet of the last step is longer than the row width learnt in the warm-up")
+        dump(lambda: dict({"packets": masked_packets(out, lens), "lengths": lens, "final_range": _r},
+                          **({"silk_burg_out": s_bo, "silk_pulses": s_pulses, "silk_nsq_state": s_st} if mixed else {})))
         kern, mean_len = celt_kernel_table(ca, L, F, steps, lens, traffic_db)
         dom = kern[0]
         kname, kms = dom["kernel"], dom["avg_launch_ms"]

@@ -27,7 +27,7 @@ def _bench(args):
 
 
 def test_two_ranks_celt_shards_on_one_gpu():
-    d = _bench(["--gpus", "2", "--frames", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "2", "--frames", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["rehearsal"] is True and d["parity_checked"] >= 1024
     assert d["value"] > 0 and d["config"]["frames_per_gpu"] == 4096
 
@@ -35,6 +35,6 @@ def test_two_ranks_celt_shards_on_one_gpu():
 def test_two_ranks_mixed_shards_on_one_gpu():
     if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libopus_ref_silkcap.so")):
         pytest.skip("capture library did not travel")
-    d = _bench(["--gpus", "2", "--workload", "mixed", "--frames", "8192", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "2", "--workload", "mixed", "--frames", "8192", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["rehearsal"] is True
     assert d["roofline"]["silk_records_per_gpu"] == 1024 and d["parity_checked"] >= 1024 + 1024

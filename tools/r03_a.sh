@@ -6,10 +6,10 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 timeout -k 10 600 python3 -m pytest tests -q -m gpu -x > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log; tail -5 $O/pytest_gpu.log
-timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err && cut -c1-400 $O/bench.json
+timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err && cut -c1-400 $O/bench.json
 for occ in 0 8; do
   for f in 4096 65536; do
-    OPUSGPU_MDCT_OCC=$occ timeout -k 10 200 python3 bench.py --workload mdct --frames $f --no-cpu-baseline > $O/bench_mdct_occ${occ}_$f.json 2>> $O/bench.err && python3 - <<PY
+    OPUSGPU_MDCT_OCC=$occ timeout -k 10 200 python3 bench.py --full --workload mdct --frames $f --no-cpu-baseline > $O/bench_mdct_occ${occ}_$f.json 2>> $O/bench.err && python3 - <<PY
 import json
 d = json.load(open("$O/bench_mdct_occ${occ}_$f.json"))
 r = d["roofline"]

@@ -8,7 +8,7 @@ cd $R
 timeout -k 10 600 python3 -m pytest tests/test_mdct_gpu.py tests/test_encode_gpu.py tests/test_decode_gpu.py tests/test_hooks_gpu.py -q -m gpu -x > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log; tail -3 $O/pytest_gpu.log
 for pre in 1 2 4; do
   for f in 4096 65536; do
-    OPUSGPU_MDCT_PRE=$pre timeout -k 10 200 python3 bench.py --workload mdct --frames $f --no-cpu-baseline > $O/bench_mdct_pre${pre}_$f.json 2>> $O/bench.err && python3 - <<PY
+    OPUSGPU_MDCT_PRE=$pre timeout -k 10 200 python3 bench.py --full --workload mdct --frames $f --no-cpu-baseline > $O/bench_mdct_pre${pre}_$f.json 2>> $O/bench.err && python3 - <<PY
 import json
 d = json.load(open("$O/bench_mdct_pre${pre}_$f.json"))
 r = d["roofline"]
@@ -16,7 +16,7 @@ print("mdct pre $pre frames $f: %.1f M frames/s  %s %.5f ms other %.5f ms  frac 
 PY
   done
 done
-timeout -k 10 300 python3 bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err && python3 - <<PY
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err && python3 - <<PY
 import json
 d = json.load(open("$O/bench.json"))
 print("celt: %.3f M frames/s, %.3f ms/step" % (d["value"] / 1e6, d["ms_per_step"]), [(k["kernel"], k["avg_launch_ms"]) for k in d["roofline"]["kernels"]])

@@ -16,7 +16,7 @@ PY
 done
 OPUSGPU_MDCT_STAGGER=3 timeout -k 10 200 python3 bench.py --workload mdct --frames 65536 --no-cpu-baseline --no-parity > $O/bench_mdct_big_stg3.json 2>> $O/bench.err && cut -c1-150 $O/bench_mdct_big_stg3.json
 for l in 64 32; do
-  OPUSGPU_DD_LANES=$l timeout -k 10 300 python3 bench.py --workload silk_deldec --no-cpu-baseline > $O/bench_dd_$l.json 2>> $O/bench.err && python3 - <<PY
+  OPUSGPU_DD_LANES=$l timeout -k 10 300 python3 bench.py --full --workload silk_deldec --no-cpu-baseline > $O/bench_dd_$l.json 2>> $O/bench.err && python3 - <<PY
 import json
 d = json.load(open("$O/bench_dd_$l.json"))
 print("silk_deldec lanes $l: %.2f M records/s %.3f ms/step parity %s" % (d["value"] / 1e6, d["ms_per_step"], d["parity_checked"]))

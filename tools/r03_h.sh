@@ -4,11 +4,11 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r03_h
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --workload silk_frames --steps 1 --warmup 0 --no-cpu-baseline > $O/prep.json 2> $O/prep.err || exit 1
+python3 $R/bench.py --full --workload silk_frames --steps 1 --warmup 0 --no-cpu-baseline > $O/prep.json 2> $O/prep.err || exit 1
 for cfg in "64 64" "32 64" "32 32" "32 16" "16 32"; do
   set -- $cfg
   export OPUSGPU_SILK_LANES=$1 OPUSGPU_SILK_BITS_LANES=$2
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$1_$2 -- python3 $R/bench.py --workload silk_frames --steps 3 --warmup 1 --no-cpu-baseline > $O/b_$1_$2.json 2> $O/b_$1_$2.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$1_$2 -- python3 $R/bench.py --full --workload silk_frames --steps 3 --warmup 1 --no-cpu-baseline > $O/b_$1_$2.json 2> $O/b_$1_$2.err || exit 1
   echo "== lanes pitch=$1 bits=$2"; python3 - <<PY
 import csv,glob,json
 d=json.loads(open("$O/b_$1_$2.json").read().strip().splitlines()[-1]); print(" ms_per_step", d["ms_per_step"], "parity", str(d.get("parity_checked"))[:60])

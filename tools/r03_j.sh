@@ -7,9 +7,9 @@ cd $R
 timeout -k 10 900 python3 -m pytest tests/test_silk_gpu.py tests/test_hooks_gpu.py -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
 for w in silk silk_deldec; do
-  python3 $R/bench.py --workload $w --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $O/prep_$w.err
+  python3 $R/bench.py --full --workload $w --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $O/prep_$w.err
   rm -rf $O/st_$w
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$w -- python3 $R/bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/b_$w.json 2> $O/b_$w.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$w -- python3 $R/bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/b_$w.json 2> $O/b_$w.err
   cut -c1-250 $O/b_$w.json
   python3 - <<PY
 import csv,glob

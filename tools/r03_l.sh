@@ -7,7 +7,7 @@ cd $R
 timeout -k 10 900 python3 -m pytest tests/test_encode_gpu.py tests/test_fuzz_gpu.py -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
 for i in 1 2; do
-timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/b$i.json 2> $O/b$i.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/b$i.json 2> $O/b$i.err || exit 1
 python3 - <<PY
 import json
 d=json.loads(open("$O/b$i.json").read().strip().splitlines()[-1])

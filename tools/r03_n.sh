@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 900 python3 -m pytest tests/test_decode_gpu.py tests/test_hooks_gpu.py -x -q -m gpu -k "decode or quant_all_bands or dec" > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py --workload decode --steps 10 --warmup 2 --no-cpu-baseline > $O/b.json 2> $O/b.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full --workload decode --steps 10 --warmup 2 --no-cpu-baseline > $O/b.json 2> $O/b.err || exit 1
 python3 - <<PY
 import json
 d=json.loads(open("$O/b.json").read().strip().splitlines()[-1])

@@ -6,8 +6,8 @@ mkdir -p $O
 cd $R
 for a in ${LANES_LIST:-32 64}; do
   export OPUSGPU_LANE_FRAMES=$a
-  timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/enc_$a.json 2> $O/enc_$a.err || exit 1
-  timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --workload decode > $O/dec_$a.json 2> $O/dec_$a.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/enc_$a.json 2> $O/enc_$a.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --workload decode > $O/dec_$a.json 2> $O/dec_$a.err || exit 1
   python3 - <<PY
 import json
 for w in ("enc","dec"):

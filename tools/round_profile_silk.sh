@@ -9,8 +9,8 @@ cd /tmp && export TMPDIR=/tmp
 for w in silk_frames silk_frames_cbr silk_streams silk_analysis silk_pred silk_nlsf; do
   # corpus capture (worker interpreters) and any stale checker library are built by a PLAIN python3 run first: nothing
   # under the profiler may start child processes (bench.py refuses to, tests/silk_corpus.py under_profiler)
-  python3 $R/bench.py --workload $w --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_prepare_$w.json 2> $O/prepare_$w.err || { echo "$w prepare failed"; continue; }
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -- python3 $R/bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_prof_$w.json 2> $O/prof_$w.err
+  python3 $R/bench.py --full --workload $w --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_prepare_$w.json 2> $O/prepare_$w.err || { echo "$w prepare failed"; continue; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -- python3 $R/bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_prof_$w.json 2> $O/prof_$w.err
   echo "$w rc=$?"; cut -c1-200 $O/bench_prof_$w.json
 done
 w=silk_frames
@@ -25,7 +25,7 @@ pmc_passes() {
   rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_SCA --output-format csv -d $O/${w}_pmc2 -- python3 $R/bench.py --workload $w --steps 1 --warmup 0 --no-cpu-baseline --no-parity > /dev/null 2>> $O/prof_pmc_$w.err
   echo "pmc $w rc=$?"
 }
-python3 $R/bench.py --workload silk_lpc --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_prepare_silk_lpc.json 2> $O/prepare_silk_lpc.err   # its corpus, outside the profiler
+python3 $R/bench.py --full --workload silk_lpc --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_prepare_silk_lpc.json 2> $O/prepare_silk_lpc.err   # its corpus, outside the profiler
 pmc_passes silk_frames && pmc_passes silk_nlsf && pmc_passes silk_lpc
 # instruction-fetch stalls (the analysis kernels are long straight-line code); last, since the counter names may not exist
 w=silk_frames
