@@ -1,39 +1,35 @@
-// celt_enc_kernel.hip -- batched Opus CELT-only encode for gfx950 (BASELINE config #3).
+// celt_enc_kernel.hip -- batched Opus CELT-only encode for gfx950 (BASELINE config #3): opusgpu_encode_batch.
 //
-// One 64-lane wavefront encodes one 20 ms frame (workgroup = one wave), in two kernels so that each
-// phase keeps only its own working set in LDS (see FrontLds / BackLds in celt_enc_front.h):
-//   celt_front_kernel  PCM -> FrameMid   (dc_reject, pre-emphasis, pitch pre-filter, transient analysis,
-//                                         MDCT, band energies, normalisation): ~23 KB LDS, 6 waves/CU
-//   celt_back_kernel   FrameMid -> packet (TF, coarse/fine energy, allocation, PVQ, range coder):
-//                                         ~9.6 KB LDS, 16 waves/CU -- the serial, latency-bound 70 %
-// FrameMid records live in a caller-provided HBM workspace; batches larger than the workspace are
-// processed in chunks on the same stream. Frames are independent units (streams advance one frame per
-// call), so the batch shards across workgroups, CUs and GPUs with no communication.
+// One pipeline of five kernels per chunk of frames, each stage with the mapping of frames onto wavefronts it wants
+// (DESIGN.md section 2); what a stage leaves for the next lies in a caller-provided HBM workspace, per frame one
+// FrameMid record + the [2][1080] int32 time signal in_ws:
+//   celt_dc_reject_kernel       pcm -> FrameMid.X (planar int16), hp_mem. Lane per (frame, channel), no LDS.
+//                               (celt_stage_kernels.hip)
+//   celt_front1_kernel          FrameMid.X, stream state -> in_ws after the pitch pre-filter; scalars + the first
+//                               range-coder bytes -> FrameMid; in_mem / prefilter_mem of the stream. Wave per frame,
+//                               13.9 KB LDS per workgroup, 11 wavefronts per CU.
+//   celt_transient_tile_kernel  in_ws (twice) -> FrameMid.trans_unmask[2]. Lane per (frame, channel), 64 rows per
+//                               wavefront tiled through LDS, 78.5 KB per workgroup, 2 wavefronts per CU.
+//                               (celt_stage_kernels.hip)
+//   celt_front2_kernel          in_ws, FrameMid -> MDCT, band energies, patch_transient_decision, normalised bands X
+//                               -> FrameMid. Wave per frame, 8.7 KB LDS per workgroup, 16 wavefronts per CU.
+//   celt_back_lane_kernel       FrameMid -> packet, length, final range; the rest of the stream state (TF, coarse/fine
+//                               energy, allocation, PVQ, range coder). Lane per frame, 64 frames per wavefront, 40.6 KB
+//                               LDS per 64-frame workgroup, one wavefront per SIMD = 4 per CU.
+//                               (celt_back_lane_kernel.hip)
+// Batches larger than the workspace are processed in chunks on the same stream. Frames are independent units (streams
+// advance one frame per call), so the batch shards across workgroups, CUs and GPUs with no communication.
+// The first design -- one wavefront per frame end to end, celt_front_kernel + celt_back_kernel -- lives on as a
+// cross-check in the diagnostic library (celt_enc_xcheck_diag.hip), not here.
 //
 // Replaces, for 48 kHz / 20 ms / restricted-lowdelay / fullband: opus_encode() (opus-fix/src/opus_encoder.c:2007)
 // -> opus_encode_native (:938) -> celt_encode_with_ec (opus-fix/celt/celt_encoder.c:1379).
-#include <stdlib.h>
 #include "celt_enc.h"
 #include "opusgpu_internal.h"
-extern "C" void opusgpu_launch_dc_reject(const void *states, const int16_t *pcm, void *mid, int n, hipStream_t s);
-extern "C" void opusgpu_launch_transient(void *mid, const int32_t *in_ws, int n, hipStream_t s);
-extern "C" void opusgpu_launch_back_lane(const opusgpu_celt_config *cfg, void *states, const void *mid, unsigned char *out,
-                                         int out_stride, int32_t *out_len, uint32_t *out_rng, int n, hipStream_t s);
 
 namespace ca {
 
-__global__ __launch_bounds__(64, 2) void celt_front_kernel(opusgpu_celt_config cfg, opusgpu_celt_state *states,
-                                                           const i16 *__restrict__ pcm, FrameMid *__restrict__ mid, int nframes)
-{
-    __shared__ FrontLds F;
-    for (int n = blockIdx.x; n < nframes; n += gridDim.x) {
-        opusgpu_celt_state *st = states ? states + n : nullptr;
-        celt_encode_front(F, cfg, st, st, pcm + (size_t)n * FRAME * cfg.channels, mid + n);
-        wave_sync();
-    }
-}
-
-// Split front phase (default pipeline): phase 1 = rate bookkeeping .. pitch pre-filter, phase 2 = MDCT ..
+// The front phase in two kernels: phase 1 = rate bookkeeping .. pitch pre-filter, phase 2 = MDCT ..
 // normalisation; the serial dc_reject and transient stages run in celt_stage_kernels.hip in between.
 __global__ __launch_bounds__(64, 3) void celt_front1_kernel(opusgpu_celt_config cfg, opusgpu_celt_state *states,
                                                             FrameMid *__restrict__ mid, i32 *__restrict__ in_ws, int nframes)
@@ -59,22 +55,6 @@ __global__ __launch_bounds__(64, 4) void celt_front2_kernel(opusgpu_celt_config 
         if (lane() == 0) { F.in_g = in; F.x_g = mid[n].X; }
         wave_sync();
         celt_encode_front_phase<2>(F, cfg, nullptr, nullptr, nullptr, mid + n, nullptr, in);
-        wave_sync();
-    }
-}
-
-__global__ __launch_bounds__(64, 4) void celt_back_kernel(opusgpu_celt_config cfg, opusgpu_celt_state *states,
-                                                          const FrameMid *__restrict__ mid, u8 *__restrict__ out, int out_stride,
-                                                          int *__restrict__ out_len, u32 *__restrict__ out_rng, int nframes)
-{
-    __shared__ BackLds F;
-    for (int n = blockIdx.x; n < nframes; n += gridDim.x) {
-        opusgpu_celt_state *st = states ? states + n : nullptr;
-        FrameResult r = celt_encode_back(F, cfg, mid + n, st, out + (size_t)n * out_stride);
-        if (lane() == 0) {
-            out_len[n] = r.bytes;
-            out_rng[n] = r.final_range;
-        }
         wave_sync();
     }
 }
@@ -145,10 +125,13 @@ extern "C" size_t opusgpu_encode_workspace_bytes(int n_frames)
     return n_frames <= 0 ? 0 : (size_t)n_frames * WS_FRAME_BYTES;
 }
 
-extern "C" int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_states, const int16_t *d_pcm,
-                                    unsigned char *d_out, int out_stride, int32_t *d_out_len, uint32_t *d_out_rng,
-                                    int n_frames, void *d_workspace, size_t workspace_bytes, void *stream)
+// argument checks + workspace layout of opusgpu_encode_batch (opusgpu_internal.h): chunk FrameMid records, then chunk in_ws rows
+extern "C" int opusgpu_encode_batch_args(const opusgpu_celt_config *cfg, const int16_t *d_pcm, const unsigned char *d_out, int out_stride,
+                                         const int32_t *d_out_len, const uint32_t *d_out_rng, int n_frames, void *d_workspace,
+                                         size_t workspace_bytes, size_t *chunk, int32_t **in_ws)
 {
+    *chunk = 0;
+    *in_ws = nullptr;
     int rc = config_ok(cfg);
     if (rc != OPUSGPU_OK) return rc;
     if (n_frames < 0) return OPUSGPU_BAD_ARG;
@@ -156,52 +139,56 @@ extern "C" int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_stat
     if (!d_pcm || !d_out || !d_out_len || !d_out_rng || !d_workspace) return OPUSGPU_BAD_ARG;
     int maxbytes = cfg->max_data_bytes < 1276 ? cfg->max_data_bytes : 1276;
     if (out_stride < ((maxbytes + 3) & ~3) || (out_stride & 3)) return OPUSGPU_BUFFER_TOO_SMALL;
-    size_t chunk = workspace_bytes / WS_FRAME_BYTES;
-    if (chunk == 0) return OPUSGPU_BUFFER_TOO_SMALL;
-    const int cus = opusgpu_num_cus();
+    *chunk = workspace_bytes / WS_FRAME_BYTES;
+    if (*chunk == 0) return OPUSGPU_BUFFER_TOO_SMALL;
+    *in_ws = (int32_t *)((char *)d_workspace + *chunk * sizeof(FrameMid));
+    return OPUSGPU_OK;
+}
+
+// persistent grids sized to what a CU holds: 13.9 KB of LDS per workgroup (11) / 8.7 KB at <= 128 VGPRs (16)
+enum { FRONT1_WAVES = 11, FRONT2_WAVES = 16 };
+
+extern "C" void opusgpu_launch_front1(const opusgpu_celt_config *cfg, void *states, void *mid, int32_t *in_ws, int n, hipStream_t s)
+{
+    const int cus = opusgpu_num_cus(), g = n < cus * FRONT1_WAVES ? n : cus * FRONT1_WAVES;
+    hipLaunchKernelGGL(celt_front1_kernel, dim3(g), dim3(64), 0, s, *cfg, (opusgpu_celt_state *)states, (FrameMid *)mid, in_ws, n);
+}
+
+extern "C" void opusgpu_launch_front2(const opusgpu_celt_config *cfg, void *mid, int32_t *in_ws, int n, hipStream_t s)
+{
+    const int cus = opusgpu_num_cus(), g = n < cus * FRONT2_WAVES ? n : cus * FRONT2_WAVES;
+    hipLaunchKernelGGL(celt_front2_kernel, dim3(g), dim3(64), 0, s, *cfg, (FrameMid *)mid, in_ws, n);
+}
+
+extern "C" int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_states, const int16_t *d_pcm,
+                                    unsigned char *d_out, int out_stride, int32_t *d_out_len, uint32_t *d_out_rng,
+                                    int n_frames, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    size_t chunk;
+    int32_t *in_ws;
+    int rc = opusgpu_encode_batch_args(cfg, d_pcm, d_out, out_stride, d_out_len, d_out_rng, n_frames, d_workspace, workspace_bytes,
+                                       &chunk, &in_ws);
+    if (rc != OPUSGPU_OK || n_frames == 0) return rc;
     opusgpu_celt_state *st = (opusgpu_celt_state *)d_states;
-    FrameMid *mid = (FrameMid *)d_workspace;
-    i32 *in_ws = (i32 *)((char *)d_workspace + chunk * sizeof(FrameMid));
+    void *mid = d_workspace;
     hipStream_t s = (hipStream_t)stream;
-    // default: one lane per frame for the serial back phase; OPUSGPU_BACK_WAVE=1 selects the one-wave-per-frame kernel
-    // (kept for the stage-stamp diagnostics and as a cross-check); OPUSGPU_FRONT_FUSED=1: the whole front phase in one
-    // wave-per-frame kernel (cross-check / diagnostics). Read once per call, not per chunk.
-    const bool lane_back = getenv("OPUSGPU_BACK_WAVE") == nullptr;
-    const bool fused_front = getenv("OPUSGPU_FRONT_FUSED") != nullptr;
     for (size_t first = 0; first < (size_t)n_frames; first += chunk) {
         int n = (int)(((size_t)n_frames - first) < chunk ? ((size_t)n_frames - first) : chunk);
-        int g1 = n < cus * 7 ? n : cus * 7;          // 22.8 KB LDS per workgroup -> 7 resident per CU (measured best)
-        int g2 = n < cus * 16 ? n : cus * 16;        // ~9.6 KB LDS per workgroup -> 16 resident per CU
-        int slot;
-        if (fused_front) {
-            slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_FRONT, s);
-            hipLaunchKernelGGL(celt_front_kernel, dim3(g1), dim3(64), 0, s, *cfg, st ? st + first : nullptr,
-                               d_pcm + first * FRAME * cfg->channels, mid, n);
-            opusgpu_timing_end(slot, s);
-        } else {
-            slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_DC_REJECT, s);
-            opusgpu_launch_dc_reject(st ? st + first : nullptr, d_pcm + first * FRAME * cfg->channels, mid, n, s);
-            opusgpu_timing_end(slot, s);
-            // persistent grids sized to what a CU holds: 13.9 KB of LDS per workgroup (11) / 8.7 KB at <= 128 VGPRs (16)
-            static const int f2_waves = getenv("OPUSGPU_FRONT2_WAVES") ? atoi(getenv("OPUSGPU_FRONT2_WAVES")) : 16;
-            const int gf1 = n < cus * 11 ? n : cus * 11, gf2 = n < cus * f2_waves ? n : cus * f2_waves;
-            slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_FRONT1, s);
-            hipLaunchKernelGGL(celt_front1_kernel, dim3(gf1), dim3(64), 0, s, *cfg, st ? st + first : nullptr, mid, in_ws, n);
-            opusgpu_timing_end(slot, s);
-            slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_TRANSIENT, s);
-            opusgpu_launch_transient(mid, in_ws, n, s);
-            opusgpu_timing_end(slot, s);
-            slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_FRONT2, s);
-            hipLaunchKernelGGL(celt_front2_kernel, dim3(gf2), dim3(64), 0, s, *cfg, mid, in_ws, n);
-            opusgpu_timing_end(slot, s);
-        }
-        slot = opusgpu_timing_begin(lane_back ? OPUSGPU_KERNEL_CELT_BACK_LANE : OPUSGPU_KERNEL_CELT_BACK, s);
-        if (lane_back)
-            opusgpu_launch_back_lane(cfg, st ? st + first : nullptr, mid, d_out + first * (size_t)out_stride, out_stride,
-                                     d_out_len + first, d_out_rng + first, n, s);
-        else
-        hipLaunchKernelGGL(celt_back_kernel, dim3(g2), dim3(64), 0, s, *cfg, st ? st + first : nullptr, mid,
-                           d_out + first * (size_t)out_stride, out_stride, d_out_len + first, d_out_rng + first, n);
+        opusgpu_celt_state *st_n = st ? st + first : nullptr;
+        int slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_DC_REJECT, s);
+        opusgpu_launch_dc_reject(st_n, d_pcm + first * FRAME * cfg->channels, mid, n, s);
+        opusgpu_timing_end(slot, s);
+        slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_FRONT1, s);
+        opusgpu_launch_front1(cfg, st_n, mid, in_ws, n, s);
+        opusgpu_timing_end(slot, s);
+        slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_TRANSIENT, s);
+        opusgpu_launch_transient(mid, in_ws, n, s);
+        opusgpu_timing_end(slot, s);
+        slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_FRONT2, s);
+        opusgpu_launch_front2(cfg, mid, in_ws, n, s);
+        opusgpu_timing_end(slot, s);
+        slot = opusgpu_timing_begin(OPUSGPU_KERNEL_CELT_BACK_LANE, s);
+        opusgpu_launch_back_lane(cfg, st_n, mid, d_out + first * (size_t)out_stride, out_stride, d_out_len + first, d_out_rng + first, n, s);
         opusgpu_timing_end(slot, s);
     }
     return opusgpu_check_launch();

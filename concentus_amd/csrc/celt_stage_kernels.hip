@@ -3,7 +3,6 @@
 #include "celt_enc.h"
 #include "celt_stage_lane.h"
 #include "opusgpu_internal.h"
-#include <stdlib.h>
 
 namespace ca {
 
@@ -23,17 +22,9 @@ __global__ __launch_bounds__(256) void celt_dc_reject_kernel(const opusgpu_celt_
     mid[f].hp_mem[2 * c + 1] = hp[1];
 }
 
-// transient metric per channel: in_ws [n][2][1080] int32 -> mid[f].trans_unmask[c]; mid[f].X is scratch here
-__global__ __launch_bounds__(256) void celt_transient_kernel(FrameMid *__restrict__ mid, const i32 *__restrict__ in_ws, int nframes)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int f = t >> 1, c = t & 1;
-    if (f >= nframes) return;
-    mid[f].trans_unmask[c] = stage_transient_channel(in_ws + ((size_t)f * 2 + c) * (FRAME + OVL), mid[f].X + c * FRAME);
-}
-
 // ---- transient metric, tiled through LDS ---------------------------------------------------------------------------
-// Same arithmetic as stage_transient_channel (celt_stage_lane.h), different data movement. One wavefront = 64 rows
+// in_ws [n][2][1080] int32 -> mid[f].trans_unmask[c]. Same arithmetic as stage_transient_channel (celt_stage_lane.h; the
+// streaming lane kernel built on it is a cross-check in celt_enc_xcheck_diag.hip), different data movement. One wavefront = 64 rows
 // (32 frames x 2 channels) of in_ws. Per lane the row is a 4 320-byte stream at a 4 320-byte stride from its
 // neighbours': read 16 bytes at a time every lane pulls its own cache line through L1 again and again (measured 2.6 GB
 // of HBM traffic per 65 536 frames for 0.57 GB of input). Here the wavefront loads the rows tile by tile (40 samples x
@@ -180,9 +171,5 @@ extern "C" void opusgpu_launch_dc_reject(const void *states, const int16_t *pcm,
 
 extern "C" void opusgpu_launch_transient(void *mid, const int32_t *in_ws, int n, hipStream_t s)
 {
-    // default: rows tiled through LDS; OPUSGPU_TRANSIENT_LANE=1 selects the streaming lane kernel (cross-check)
-    if (getenv("OPUSGPU_TRANSIENT_LANE"))
-        hipLaunchKernelGGL(ca::celt_transient_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, s, (ca::FrameMid *)mid, in_ws, n);
-    else
-        hipLaunchKernelGGL(ca::celt_transient_tile_kernel, dim3((2 * n + 63) / 64), dim3(64), 0, s, (ca::FrameMid *)mid, in_ws, n);
+    hipLaunchKernelGGL(ca::celt_transient_tile_kernel, dim3((2 * n + 63) / 64), dim3(64), 0, s, (ca::FrameMid *)mid, in_ws, n);
 }

@@ -1,5 +1,6 @@
 // runtime.hip -- process-level plumbing of libopusgpu.so: version, error strings, device queries.
 #include <stdio.h>
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include "opusgpu_internal.h"
@@ -28,16 +29,19 @@ extern "C" const char *opusgpu_strerror(int error)
     return msg[-error];
 }
 
+// CUs of the current device, cached per device index; 256 where the device cannot be asked
 extern "C" int opusgpu_num_cus(void)
 {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-        cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    static std::atomic<int> cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int n = cus[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
+        if (n <= 0) n = 256;
+        cus[dev].store(n, std::memory_order_relaxed);
     }
-    return cus;
+    return n;
 }
 
 // ---- optional per-kernel timing (HIP events on the launch stream) ----
@@ -153,13 +157,4 @@ extern "C" int opusgpu_silk_bad_records(void *stream)
         hipMemsetAsync(p, 0, sizeof(int), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return OPUSGPU_INTERNAL_ERROR;
     return n;
-}
-
-// Records per wavefront of the scratch-resident SILK analysis kernels (silk_pitch_kernels.hip, silk_nlsf_kernels.hip). Read per
-// call so that tests and sweeps can compare the mappings.
-extern "C" int opusgpu_silk_lanes_per_block(void)
-{
-    const char *e = getenv("OPUSGPU_SILK_LANES");
-    const int v = e ? atoi(e) : 64;
-    return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 64;
 }

@@ -95,7 +95,7 @@ extern "C" int opusgpu_silk_process_nlsfs_batch(const opusgpu_process_nlsf_in *d
     if (!d_in || !d_out) return OPUSGPU_BAD_ARG;
     int *bad = opusgpu_bad_record_counter();
     if (!bad) return OPUSGPU_ALLOC_FAIL;
-    const int lpb = opusgpu_silk_lanes_per_block();
+    const int lpb = SILK_LANES_PER_BLOCK;
     hipLaunchKernelGGL(silk_process_nlsfs_kernel, dim3((n + lpb - 1) / lpb), dim3(lpb), 0, (hipStream_t)stream, d_in, d_out, n, bad);
     return opusgpu_check_launch();
 }

@@ -54,9 +54,7 @@ extern "C" int opusgpu_silk_find_pitch_lags_batch(const opusgpu_find_pitch_lags_
     if (!d_in || !d_out) return OPUSGPU_BAD_ARG;
     int *bad = opusgpu_bad_record_counter();
     if (!bad) return OPUSGPU_ALLOC_FAIL;
-    // Lanes per wavefront: the kernel is bound by the latency of one frame's serial chain (its work arrays live in scratch memory),
-    // not by issue slots, so partially filled wavefronts -- more of them per SIMD -- hide that latency (OPUSGPU_SILK_LANES=16/32/64).
-    const int lpb = opusgpu_silk_lanes_per_block();
+    const int lpb = SILK_LANES_PER_BLOCK;
     hipLaunchKernelGGL(silk_find_pitch_lags_kernel, dim3((n + lpb - 1) / lpb), dim3(lpb), 0, (hipStream_t)stream, d_in, d_out, n, bad);
     return opusgpu_check_launch();
 }

@@ -86,13 +86,16 @@ SYMBOLS = [
     ("opusgpu_silk_NSQ_del_dec", None, [_vp] * 13 + [_i, _i]),
 ]
 
-# include/opusgpu_diag.h: the stage-stamp builds, in a library of their own (tools/stage_profile*.py only)
+# include/opusgpu_diag.h: the stage-stamp builds (tools/stage_profile*.py) and the cross-check builds of superseded
+# stages (the tests), in a library of their own
 DIAG_LIB_PATH = os.path.join(_HERE, "libopusgpu_diag.so")
 DIAG_SYMBOLS = [
     ("opusgpu_decode_lane_diag", _i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     ("opusgpu_back_lane_diag", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("opusgpu_encode_batch_diag", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp]),
+    ("opusgpu_encode_batch_xcheck", _i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, C.c_size_t, C.c_uint, _vp]),
 ]
+XCHECK_FRONT_FUSED, XCHECK_BACK_WAVE, XCHECK_TRANSIENT_LANE = 1, 2, 4
 
 _lib = None
 _diag = None
@@ -123,7 +126,7 @@ def load():
 
 
 def load_diag():
-    """The diagnostic library (stage stamps); raises if it has not been built (`make -C concentus_amd/csrc diag`)."""
+    """The diagnostic library (stage stamps, cross-checks); raises if it has not been built (`make -C concentus_amd/csrc diag`)."""
     global _diag
     if _diag is None:
         load()

@@ -44,7 +44,10 @@ int opusgpu_num_cus(void);
  * of opusgpu_encode_batch / opusgpu_decode_batch is bracketed by HIP events recorded on the launch stream.
  * opusgpu_kernel_timing_read waits for the recorded launches, writes the summed duration (ms) and the
  * launch count per kernel id into ms_sum[0..n_kernels) / launches[0..n_kernels), and forgets them.
- * No counterpart in the reference (its timing is wall clock in src/opus_demo.c:750-800). */
+ * No counterpart in the reference (its timing is wall clock in src/opus_demo.c:750-800).
+ * Ids 0 and 1 are the wave-per-frame kernels of the first design; the product library no longer launches them (they are
+ * cross-checks in the diagnostic library, untimed), so their launch counts stay 0. The ids keep their values: callers index
+ * the table by position. */
 #define OPUSGPU_KERNEL_CELT_FRONT 0
 #define OPUSGPU_KERNEL_CELT_BACK  1
 #define OPUSGPU_KERNEL_CELT_BACK_LANE 2

@@ -35,7 +35,8 @@ def test_header_symbols_all_exported():
 
 
 def test_diag_library_is_separate():
-    """The stage-stamp diagnostic builds live in libopusgpu_diag.so (include/opusgpu_diag.h), not in the product library."""
+    """The stage-stamp diagnostic builds and the cross-check builds of superseded stages live in libopusgpu_diag.so
+    (include/opusgpu_diag.h), not in the product library."""
     lib = _ensure_built()
     src = open(os.path.join(ROOT, "include", "opusgpu_diag.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
@@ -43,10 +44,19 @@ def test_diag_library_is_separate():
     assert declared == {name for name, _, _ in lib.DIAG_SYMBOLS}
     out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
     assert not [l for l in out.splitlines() if "_diag" in l], "diagnostic code in the product library"
+    # the cross-check entry and the superseded kernels it runs (handles and host stubs are exported under mangled names)
+    gone = ("opusgpu_encode_batch_xcheck", "celt_front_kernel", "celt_back_kernel", "celt_transient_kernel")
+    assert not [l for l in out.splitlines() if any(g in l for g in gone)], "cross-check code in the product library"
+    # ... and no kernel of the product library is chosen by an environment variable any more
+    blob = open(lib.LIB_PATH, "rb").read()
+    for var in ("OPUSGPU_BACK_WAVE", "OPUSGPU_FRONT_FUSED", "OPUSGPU_TRANSIENT_LANE", "OPUSGPU_FRONT2_WAVES", "OPUSGPU_SILK_LANES",
+                "OPUSGPU_SILK_BITS_LANES"):
+        assert var.encode() not in blob, var
     if os.path.exists(lib.DIAG_LIB_PATH):
         out = subprocess.check_output(["nm", "-D", "--defined-only", lib.DIAG_LIB_PATH], text=True)
         exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
         assert declared <= exported
+        assert "opusgpu_encode_batch_xcheck" in exported
 
 
 def test_python_binding_covers_header():

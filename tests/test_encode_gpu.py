@@ -55,6 +55,27 @@ def _gpu_encode(ca, pcm, fps, cfgvals):
     return outs, lens, rngs
 
 
+def _gpu_encode_xcheck(ca, pcm, cfgvals, variant, ws_frames=None):
+    """Independent frames through opusgpu_encode_batch_xcheck of the diagnostic library (load_diag() raises where it is not
+    built): the pipeline with the stages in `variant` replaced, in a workspace of ws_frames frames (default: the batch)."""
+    import torch
+    D = ca.lib.load_diag()
+    cfg = _cfg(ca, cfgvals)
+    n = pcm.shape[0]
+    stride = ca.encoder.out_stride_for(cfg)
+    d = torch.from_numpy(np.ascontiguousarray(pcm)).cuda()
+    out = torch.zeros((n, stride), dtype=torch.uint8, device="cuda")
+    lens = torch.empty((n,), dtype=torch.int32, device="cuda")
+    rng = torch.empty((n,), dtype=torch.int32, device="cuda")
+    ws = torch.empty((ca.lib.load().opusgpu_encode_workspace_bytes(n if ws_frames is None else ws_frames),),
+                     dtype=torch.uint8, device="cuda")
+    rc = D.opusgpu_encode_batch_xcheck(C.byref(cfg), None, d.data_ptr(), out.data_ptr(), stride, lens.data_ptr(), rng.data_ptr(),
+                                       n, ws.data_ptr(), ws.numel(), variant, ca.lib.current_stream_handle())
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    return out.cpu().numpy(), lens.cpu().numpy(), rng.cpu().numpy().view(np.uint32)
+
+
 @pytest.mark.parametrize("case", ec.cases(), ids=lambda c: c[0])
 def test_gpu_matches_golden_packets(ca, case):
     name, _kind, _n, fps, _seed, cfgvals = case
@@ -203,19 +224,16 @@ def test_bad_configs_rejected(ca):
     assert out.shape[0] == 0
 
 
-def test_wave_per_frame_back_kernel_agrees_with_lane_per_frame(ca, monkeypatch):
-    """The library ships two mappings of the back phase (one lane per frame: default; one wave per frame:
-    OPUSGPU_BACK_WAVE=1, also the build the stage-stamp diagnostics use). Same sources, same packets."""
+def test_wave_per_frame_back_kernel_agrees_with_lane_per_frame(ca):
+    """Two mappings of the back phase are built from the same sources (one lane per frame: the product; one wave per frame:
+    OPUSGPU_XCHECK_BACK_WAVE of the diagnostic library, also the build the stage-stamp diagnostics use). Same packets."""
     gm = ec.golden_module()
     pcm = gm.synth_pcm("music", 1024, 99)
     a = _gpu_encode(ca, pcm, 1, (96000, 1, 0, 10))
-    monkeypatch.setenv("OPUSGPU_BACK_WAVE", "1")
-    b = _gpu_encode(ca, pcm, 1, (96000, 1, 0, 10))
-    monkeypatch.delenv("OPUSGPU_BACK_WAVE")
+    b = _gpu_encode_xcheck(ca, pcm, (96000, 1, 0, 10), ca.lib.XCHECK_BACK_WAVE)
     ec.assert_packets_equal(a[0], a[1], a[2], b[0], b[1], b[2], "lane vs wave back kernel")
     pk, ln, rg = ec.load_case("music_vbr_indep")[1:]
-    monkeypatch.setenv("OPUSGPU_BACK_WAVE", "1")
-    w = _gpu_encode(ca, ec.load_case("music_vbr_indep")[0], 1, (96000, 1, 0, 10))
+    w = _gpu_encode_xcheck(ca, ec.load_case("music_vbr_indep")[0], (96000, 1, 0, 10), ca.lib.XCHECK_BACK_WAVE)
     ec.assert_packets_equal(w[0], w[1], w[2], pk, ln, rg, "wave back kernel vs golden")
 
 
@@ -242,24 +260,23 @@ def test_frames_per_wavefront_of_the_lane_kernels(ca, monkeypatch):
         ec.assert_packets_equal(*res[32][:3], *want, "lane frames 32 vs reference")
 
 
-def test_transient_kernels_agree(ca, monkeypatch):
-    """The transient metric runs tiled through LDS (default) or as the streaming lane kernel
-    (OPUSGPU_TRANSIENT_LANE=1): same arithmetic, same packets -- noise (every frame transient), music (few) and edge
-    frames, with a ragged last tile of rows (1 001 frames = 2 002 rows)."""
+def test_transient_kernels_agree(ca):
+    """The transient metric runs tiled through LDS (the product) or as the streaming lane kernel
+    (OPUSGPU_XCHECK_TRANSIENT_LANE of the diagnostic library): same arithmetic, same packets -- noise (every frame
+    transient), music (few) and edge frames, with a ragged last tile of rows (1 001 frames = 2 002 rows)."""
     gm = ec.golden_module()
     for kind, n, seed in (("noise", 1001, 31), ("music", 515, 32), ("edge", 64, 33)):
         pcm = gm.synth_pcm(kind, n, seed)
         a = _gpu_encode(ca, pcm, 1, (96000, 1, 0, 10))
-        monkeypatch.setenv("OPUSGPU_TRANSIENT_LANE", "1")
-        b = _gpu_encode(ca, pcm, 1, (96000, 1, 0, 10))
-        monkeypatch.delenv("OPUSGPU_TRANSIENT_LANE")
+        b = _gpu_encode_xcheck(ca, pcm, (96000, 1, 0, 10), ca.lib.XCHECK_TRANSIENT_LANE)
         ec.assert_packets_equal(a[0], a[1], a[2], b[0], b[1], b[2], "transient kernels, %s" % kind)
 
 
-def test_small_workspace_chunks_the_batch(ca, monkeypatch):
+def test_small_workspace_chunks_the_batch(ca):
     """A workspace smaller than the batch is legal (include/opusgpu.h): the library then runs the pipeline over
     chunks of workspace_bytes / opusgpu_encode_workspace_bytes(1) frames. Same packets, and the fused
-    single-kernel front phase (OPUSGPU_FRONT_FUSED=1) agrees with the split pipeline."""
+    single-kernel front phase (OPUSGPU_XCHECK_FRONT_FUSED of the diagnostic library, which chunks the same way)
+    agrees with the split pipeline."""
     import torch
     gm = ec.golden_module()
     pcm = gm.synth_pcm("music", 700, 7)
@@ -268,20 +285,19 @@ def test_small_workspace_chunks_the_batch(ca, monkeypatch):
     L = ca.lib.load()
     d = torch.from_numpy(np.ascontiguousarray(pcm)).cuda()
     stride = ca.encoder.out_stride_for(cfg)
-    for fused in (False, True):
-        if fused:
-            monkeypatch.setenv("OPUSGPU_FRONT_FUSED", "1")
-        out = torch.zeros((700, stride), dtype=torch.uint8, device="cuda")
-        lens = torch.empty((700,), dtype=torch.int32, device="cuda")
-        rng = torch.empty((700,), dtype=torch.int32, device="cuda")
-        ws = torch.empty((L.opusgpu_encode_workspace_bytes(256) + 100,), dtype=torch.uint8, device="cuda")   # 256-frame chunks: 256+256+188
-        rc = L.opusgpu_encode_batch(C.byref(cfg), None, d.data_ptr(), out.data_ptr(), stride, lens.data_ptr(), rng.data_ptr(),
-                                    700, ws.data_ptr(), ws.numel(), None)
-        torch.cuda.synchronize()
-        assert rc == 0
-        ec.assert_packets_equal(out.cpu().numpy(), lens.cpu().numpy(), rng.cpu().numpy().view(np.uint32),
-                                ref[0], ref[1], ref[2], "chunked, fused=%s" % fused)
-    monkeypatch.delenv("OPUSGPU_FRONT_FUSED")
+    out = torch.zeros((700, stride), dtype=torch.uint8, device="cuda")
+    lens = torch.empty((700,), dtype=torch.int32, device="cuda")
+    rng = torch.empty((700,), dtype=torch.int32, device="cuda")
+    ws = torch.empty((L.opusgpu_encode_workspace_bytes(256) + 100,), dtype=torch.uint8, device="cuda")   # 256-frame chunks: 256+256+188
+    rc = L.opusgpu_encode_batch(C.byref(cfg), None, d.data_ptr(), out.data_ptr(), stride, lens.data_ptr(), rng.data_ptr(),
+                                700, ws.data_ptr(), ws.numel(), None)
+    torch.cuda.synchronize()
+    assert rc == 0
+    ec.assert_packets_equal(out.cpu().numpy(), lens.cpu().numpy(), rng.cpu().numpy().view(np.uint32),
+                            ref[0], ref[1], ref[2], "chunked, fused=False")
+    for variant in (ca.lib.XCHECK_FRONT_FUSED, 0):
+        x = _gpu_encode_xcheck(ca, pcm, (96000, 1, 0, 10), variant, ws_frames=256)
+        ec.assert_packets_equal(x[0], x[1], x[2], ref[0], ref[1], ref[2], "chunked, xcheck variant %d" % variant)
 
 
 @pytest.mark.parametrize("name", ["music_vbr_stream", "noise_cvbr_stream", "music_cbr_stream_cx5"])
