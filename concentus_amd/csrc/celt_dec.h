@@ -9,7 +9,7 @@
 // celt_synthesis (celt_decoder.c:287), the post-filter comb_filter (celt.c:183) and deemphasis
 // (celt_decoder.c:183), plus the CELT-only slice of opus_decode_frame (src/opus_decoder.c:200-600:
 // TOC, range decoder set-up, final range). The decoder is a serial chain per packet, so it is written as
-// scalar code for the lane-per-frame build (LANES == 1); packet loss concealment is not implemented.
+// scalar code for the lane-per-frame build (LANES == 1); packet loss concealment (celt_decode_lost) is in celt_plc.h.
 #pragma once
 #include "celt_enc_back.h"
 #include "celt_state.h"
@@ -1373,6 +1373,7 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     st->postfilter_tapset_old = st->postfilter_tapset;
 
     if (!isTransient) {
+        if (st->loss_count >= 10) CA_COUNT("plc_recover_after_10", 1);
         for (int i = 0; i < 2 * NB; i++) { oldLogE2[i] = oldLogE[i]; oldLogE[i] = oldBandE[i]; }
         const i32 max_background_increase = st->loss_count < 10 ? M * 1 : 1024;               // M*QCONST16(0.001f, DB_SHIFT)
         for (int i = 0; i < 2 * NB; i++) backgroundLogE[i] = (i16)imin(backgroundLogE[i] + max_background_increase, oldBandE[i]);
@@ -1382,6 +1383,7 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     st->rng = dec.rng;
 
     st->loss_count = 0;
+    st->started = 1;                                                                             // the Opus layer's prev_mode (src/opus_decoder.c:584)
     CA_STAMP_F(F, 11);
     if (ec_tell(dec) > 8 * len) { res.samples = OPUSGPU_INTERNAL_ERROR; return res; }
     if (dec.error) st->error = 1;

@@ -8,16 +8,21 @@
 // stream (celt_dec_synth_kernel.hip); the post-filter and de-emphasis are recurrences per channel and run one
 // lane per (stream, channel) (celt_decode_post_kernel, this file). The stream state (decode_mem, energies,
 // post-filter) and the hand-off between the three kernels live in opusgpu_celt_dec_state in HBM.
+// opusgpu_decode_batch_plc is the same pipeline with packet loss concealment (celt_plc.h): the lane kernel marks the lost streams,
+// celt_dec_plc_kernel (celt_dec_plc_kernel.hip) runs between it and the synthesis, and celt_decode_post_plc_kernel (this file)
+// adds the concealment's per-channel recurrences to the post stage.
 #define CA_LANE_FRAME 1
 #include "celt_lane_tables.h"
-#include "celt_dec.h"
+#include "celt_plc.h"
 #include "opusgpu_internal.h"
 
 namespace ca {
 
 // A = streams per wavefront (64, or 32 / 16 with 2 / 4 partly filled waves per 64-stream workgroup; see
 // celt_back_lane_kernel.hip)
-template <int A>
+// PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is the one-byte DTX packet is left to
+// the concealment kernels (celt_dec_plc_kernel.hip), which find it by st->mid_plc
+template <int A, bool PLC>
 __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu_celt_dec_state *states, const u8 *__restrict__ packets,
                                                               int packet_stride, const int *__restrict__ len,
                                                               int *__restrict__ ret, u32 *__restrict__ rng, int n)
@@ -31,7 +36,17 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
     DecWork F;
     F.lds_iy16 = (CA_AS_LDS i16 *)(g_lds_iy16 + slot);
     F.lds_pvq16 = (CA_AS_LDS i16 *)(g_lds_pvq16 + slot);
-    const int ln = len[k];
+    const int ln = PLC && !len ? 0 : len[k];
+    if (PLC) {
+        const bool lost = ln == 0 || (ln == 1 && packet_stride >= 1 && packets[(size_t)k * packet_stride] == 0xFC);
+        states[k].mid_plc = lost ? OPUSGPU_PLC_LOST : OPUSGPU_PLC_NONE;
+        if (lost) {
+            states[k].mid_valid = 0;
+            ret[k] = FRAME;
+            rng[k] = 0;
+            return;
+        }
+    }
     if (ln > packet_stride) {
         // a length past this stream's row would read the next stream's packet (or, for the last stream, past the slab)
         states[k].mid_valid = 0;
@@ -49,15 +64,20 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
 // recurrence over them, then the stores -- and the two lanes exchange their outputs (DPP) so that each writes interleaved
 // stereo 16 bytes at a time: a load, the recurrence step and a 2-byte store per sample was one exposed memory round trip per
 // sample (loads queue behind stores), 960 per channel and most of this kernel's 0.70 ms.
-__device__ __forceinline__ void celt_decode_post_pair(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+__device__ __forceinline__ void celt_postfilter_channel(opusgpu_celt_dec_state *st, int c)
 {
-    if (!st->mid_valid) return;
     const int N = FRAME;
     i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
     comb_filter_inplace_dec(out_syn, st->mid_pf_period_old, st->mid_pf_period, 120, st->mid_pf_gain_old, st->mid_pf_gain,
                             st->mid_pf_tapset_old, st->mid_pf_tapset);
     comb_filter_inplace_dec(out_syn + 120, st->mid_pf_period, st->mid_pf_period_new, N - 120, st->mid_pf_gain, st->mid_pf_gain_new,
                             st->mid_pf_tapset, st->mid_pf_tapset_new);
+}
+
+__device__ __forceinline__ void celt_deemphasis_pair(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+{
+    const int N = FRAME;
+    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
     i32 m = st->preemph_memD[c];
     const int4 *src = reinterpret_cast<const int4 *>(out_syn);
     for (int j0 = 0; j0 < N; j0 += 32) {
@@ -91,12 +111,44 @@ __device__ __forceinline__ void celt_decode_post_pair(opusgpu_celt_dec_state *st
     st->preemph_memD[c] = m;
 }
 
+__device__ __forceinline__ void celt_decode_post_pair(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+{
+    if (!st->mid_valid) return;
+    celt_postfilter_channel(st, c);
+    celt_deemphasis_pair(st, c, pcm);
+}
+
 __global__ __launch_bounds__(256) void celt_decode_post_kernel(opusgpu_celt_dec_state *states, i16 *__restrict__ pcm, int n)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = t >> 1, c = t & 1;
     if (k >= n) return;
     celt_decode_post_pair(states + k, c, pcm + (size_t)k * FRAME * 2);
+}
+
+// The post kernel of opusgpu_decode_batch_plc. A received stream (and one concealed from noise, which went through the synthesis)
+// is treated as above; a stream in the pitch-based branch first gets the per-channel tail of celt_decode_lost (celt_plc.h:
+// celt_iir, explosion check, TDAC fold); a stream without history gets zeros. Both lanes of a stream take the same way.
+__global__ __launch_bounds__(256) void celt_decode_post_plc_kernel(opusgpu_celt_dec_state *states, i16 *__restrict__ pcm, int n)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = t >> 1, c = t & 1;
+    if (k >= n) return;
+    opusgpu_celt_dec_state *st = states + k;
+    i16 *out = pcm + (size_t)k * FRAME * 2;
+    const int plc = st->mid_plc;
+    bool deemph = false;
+    if (plc == OPUSGPU_PLC_ZEROS) {
+        int4 *z = reinterpret_cast<int4 *>(out + c * FRAME);                 // each lane clears half of the stream's 3840 bytes
+        for (int j = 0; j < FRAME * 2 / 16; j++) z[j] = make_int4(0, 0, 0, 0);
+    } else if (plc == OPUSGPU_PLC_PITCH) {
+        celt_plc_tail_channel(st, c);
+        deemph = true;
+    } else if (st->mid_valid) {
+        celt_postfilter_channel(st, c);
+        deemph = true;
+    }
+    if (deemph) celt_deemphasis_pair(st, c, out);
 }
 
 // fresh decoder state (opus_decoder_create + OPUS_RESET_STATE, celt_decoder.c:1177-1190)
@@ -176,7 +228,7 @@ extern "C" int opusgpu_decode_batch(void *d_states, const unsigned char *d_packe
     {
         const int a = opusgpu_lane_frames(32);          // (decoder lane kernel: 5.06 ms at 32 streams per wavefront, 5.39 ms at 64)
         const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
-#define CA_LAUNCH(A) hipLaunchKernelGGL(ca::celt_decode_lane_kernel<A>, grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
+#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, false>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
                                         d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
         if (a == 32) CA_LAUNCH(32);
         else CA_LAUNCH(64);
@@ -188,6 +240,44 @@ extern "C" int opusgpu_decode_batch(void *d_states, const unsigned char *d_packe
     opusgpu_timing_end(slot, s);
     slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
     hipLaunchKernelGGL(ca::celt_decode_post_kernel, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s,
+                       (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
+    opusgpu_timing_end(slot, s);
+    return opusgpu_check_launch();
+}
+
+extern "C" void opusgpu_launch_dec_plc(void *states, int n, hipStream_t s);
+
+// opusgpu_decode_batch with packet loss concealment: the same lane and synthesis kernels, the concealment's wave-per-stream kernel
+// between them (it leaves at once on a received stream) and the post kernel that knows about concealed streams
+extern "C" int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                                        int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *stream)
+{
+    if (n_streams < 0) return OPUSGPU_BAD_ARG;
+    if (n_streams == 0) return OPUSGPU_OK;
+    if (!d_states || !d_pcm || !d_ret || !d_rng) return OPUSGPU_BAD_ARG;
+    if (d_len && (!d_packets || packet_stride <= 0)) return OPUSGPU_BAD_ARG;     // d_len == NULL: every stream is lost, no packets
+    if (((uintptr_t)d_pcm & 15) != 0) return OPUSGPU_BAD_ARG;
+    if (!d_len) { d_packets = nullptr; packet_stride = 0; }
+    hipStream_t s = (hipStream_t)stream;
+    int slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_LANE, s);
+    {
+        const int a = opusgpu_lane_frames(32);
+        const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
+#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, true>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
+                                        d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
+        if (a == 32) CA_LAUNCH(32);
+        else CA_LAUNCH(64);
+#undef CA_LAUNCH
+    }
+    opusgpu_timing_end(slot, s);
+    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_PLC, s);
+    opusgpu_launch_dec_plc(d_states, n_streams, s);
+    opusgpu_timing_end(slot, s);
+    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_SYNTH, s);
+    opusgpu_launch_dec_synth(d_states, n_streams, s);
+    opusgpu_timing_end(slot, s);
+    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
+    hipLaunchKernelGGL(ca::celt_decode_post_plc_kernel, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s,
                        (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
     opusgpu_timing_end(slot, s);
     return opusgpu_check_launch();

@@ -7,6 +7,7 @@
 // and stores it back. A NULL state pointer means "every frame is the first frame of its own stream"
 // (SURVEY.md 8d): the reset values below are then materialised in registers/LDS and nothing is stored.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/opusgpu.h"   /* opusgpu_celt_config */
 
@@ -55,9 +56,12 @@ typedef struct opusgpu_celt_state {
 } opusgpu_celt_state;
 
 /* Decoder counterpart: everything `struct OpusCustomDecoder` keeps past DECODER_RESET_START for a stereo
- * stream (opus-fix/celt/celt_decoder.c:66-97 and the trailing arrays :94-96; `lpc` is only used by the
- * packet loss concealment, which is not implemented). */
+ * stream (opus-fix/celt/celt_decoder.c:66-97 and the trailing arrays :94-96). `lpc` and `last_pitch_index`
+ * belong to the packet loss concealment (celt_decode_lost, celt_plc.h): the synthesis filter of the first lost
+ * frame and its pitch, reused by the losses that follow it. `started` is the Opus layer's "prev_mode != 0"
+ * (src/opus_decoder.c:259-268): set by every decoded packet, cleared by init/reset; a loss before it is zeros. */
 #define OPUSGPU_DECODE_BUFFER_SIZE 2048
+#define OPUSGPU_CELT_LPC_ORDER 24
 typedef struct opusgpu_celt_dec_state {
     uint32_t rng;
     int32_t error;
@@ -66,11 +70,14 @@ typedef struct opusgpu_celt_dec_state {
     int32_t postfilter_tapset, postfilter_tapset_old;
     int32_t preemph_memD[2];
     int32_t loss_count;
-    int32_t reserved[5];
+    int32_t last_pitch_index;
+    int32_t started;
+    int32_t reserved[3];
     int16_t oldBandE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE2[2 * OPUSGPU_CELT_NBANDS];
     int16_t backgroundLogE[2 * OPUSGPU_CELT_NBANDS];
+    int16_t lpc[2][OPUSGPU_CELT_LPC_ORDER];
     int32_t decode_mem[2][OPUSGPU_DECODE_BUFFER_SIZE + OPUSGPU_CELT_OVERLAP];
     /* hand-off between the kernels of one opusgpu_decode_batch call (not stream state): the decoded normalised
      * bands, what the synthesis and post-filter kernels need to know about the frame, and the per-stream result */
@@ -80,7 +87,26 @@ typedef struct opusgpu_celt_dec_state {
     int32_t mid_pf_period_old, mid_pf_period, mid_pf_period_new;
     int32_t mid_pf_gain_old, mid_pf_gain, mid_pf_gain_new;
     int32_t mid_pf_tapset_old, mid_pf_tapset, mid_pf_tapset_new;
+    /* ... of one opusgpu_decode_batch_plc call: what the concealment still owes this stream (OPUSGPU_PLC_*), and the energy
+     * S1 of the signal whose excitation the pitch-based branch copied (celt_decoder.c:629-634), per channel */
+    int32_t mid_plc;
+    int32_t mid_plc_S1[2];
+    int32_t mid_pad;
 } opusgpu_celt_dec_state;
+
+/* mid_plc: the stream was received / is lost and not yet looked at / has no history (zeros) / is synthesised from noise by
+ * the ordinary synthesis / waits for the per-channel tail of the pitch-based branch (celt_iir onwards) */
+#define OPUSGPU_PLC_NONE 0
+#define OPUSGPU_PLC_LOST 1
+#define OPUSGPU_PLC_ZEROS 2
+#define OPUSGPU_PLC_NOISE 3
+#define OPUSGPU_PLC_PITCH 4
+
+#ifdef __cplusplus
+/* the synthesis kernel moves decode_mem in 16-byte units, and the records of a batch lie back to back */
+static_assert(offsetof(opusgpu_celt_dec_state, decode_mem) % 16 == 0, "decode_mem must stay 16-byte aligned");
+static_assert(sizeof(opusgpu_celt_dec_state) % 16 == 0, "sizeof(opusgpu_celt_dec_state) must stay a multiple of 16");
+#endif
 
 #ifdef __cplusplus
 }

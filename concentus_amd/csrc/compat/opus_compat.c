@@ -11,9 +11,11 @@
  * include/opus_defines.h:46-60 (error codes, identical to OPUSGPU_*), :770-784 (opus_strerror, opus_get_version_string).
  * Supported region: what libopusgpu.so implements (48 kHz stereo, 20 ms, OPUS_APPLICATION_RESTRICTED_LOWDELAY);
  * everything else returns OPUS_UNIMPLEMENTED exactly where libopus would have returned OPUS_OK. */
+#define _DEFAULT_SOURCE 1            /* initstate / setstate */
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../../include/opusgpu.h"
 
 typedef struct OpusGpuEncoder OpusEncoder;
@@ -21,9 +23,20 @@ typedef struct OpusGpuDecoder OpusDecoder;
 
 #define OPUS_RESET_STATE_REQUEST 4028
 
+/* libopus never touches the C library's random generator; the HSA runtime under libopusgpu.so does (it imports srand and rand,
+ * and a process that has loaded it no longer draws the sequence it would have drawn). A caller may depend on that sequence:
+ * opus_demo -loss draws its loss pattern from rand(). So every entry point that can reach the runtime runs on a generator state
+ * of this library's own and puts the caller's back, position included, before it returns (rand() and random() share the state
+ * that initstate / setstate exchange). Like rand() itself this is not meant for concurrent callers. */
+static char g_own_rand_state[128];
+#define CALLER_RAND_KEPT(call) do { char *caller_ = initstate(1u, g_own_rand_state, sizeof g_own_rand_state); call; \
+                                    if (caller_) setstate(caller_); } while (0)
+
 OpusEncoder *opus_encoder_create(int32_t Fs, int channels, int application, int *error)
 {
-    return opusgpu_encoder_create(Fs, channels, application, error);
+    OpusEncoder *st;
+    CALLER_RAND_KEPT(st = opusgpu_encoder_create(Fs, channels, application, error));
+    return st;
 }
 
 /* opus_encoder_ctl is variadic. Every request of include/opus_defines.h:130-167 carries exactly one argument: an
@@ -33,43 +46,61 @@ int opus_encoder_ctl(OpusEncoder *st, int request, ...)
     va_list ap;
     int ret;
     va_start(ap, request);
-    if (request == OPUS_RESET_STATE_REQUEST) ret = opusgpu_encoder_ctl(st, request);
-    else if (request & 1) ret = opusgpu_encoder_ctl(st, request, va_arg(ap, void *));
-    else ret = opusgpu_encoder_ctl(st, request, va_arg(ap, int32_t));
+    if (request == OPUS_RESET_STATE_REQUEST) CALLER_RAND_KEPT(ret = opusgpu_encoder_ctl(st, request));
+    else if (request & 1) CALLER_RAND_KEPT(ret = opusgpu_encoder_ctl(st, request, va_arg(ap, void *)));
+    else CALLER_RAND_KEPT(ret = opusgpu_encoder_ctl(st, request, va_arg(ap, int32_t)));
     va_end(ap);
     return ret;
 }
 
 int32_t opus_encode(OpusEncoder *st, const int16_t *pcm, int frame_size, unsigned char *data, int32_t max_data_bytes)
 {
-    return opusgpu_encode(st, pcm, frame_size, data, max_data_bytes);
+    int32_t ret;
+    CALLER_RAND_KEPT(ret = opusgpu_encode(st, pcm, frame_size, data, max_data_bytes));
+    return ret;
 }
 
-void opus_encoder_destroy(OpusEncoder *st) { opusgpu_encoder_destroy(st); }
+void opus_encoder_destroy(OpusEncoder *st) { CALLER_RAND_KEPT(opusgpu_encoder_destroy(st)); }
 
-OpusDecoder *opus_decoder_create(int32_t Fs, int channels, int *error) { return opusgpu_decoder_create(Fs, channels, error); }
+OpusDecoder *opus_decoder_create(int32_t Fs, int channels, int *error)
+{
+    OpusDecoder *st;
+    CALLER_RAND_KEPT(st = opusgpu_decoder_create(Fs, channels, error));
+    return st;
+}
 
 int opus_decoder_ctl(OpusDecoder *st, int request, ...)
 {
     va_list ap;
     int ret;
     va_start(ap, request);
-    if (request == OPUS_RESET_STATE_REQUEST) ret = opusgpu_decoder_ctl(st, request);
-    else if (request & 1) ret = opusgpu_decoder_ctl(st, request, va_arg(ap, void *));
-    else ret = opusgpu_decoder_ctl(st, request, va_arg(ap, int32_t));
+    if (request == OPUS_RESET_STATE_REQUEST) CALLER_RAND_KEPT(ret = opusgpu_decoder_ctl(st, request));
+    else if (request & 1) CALLER_RAND_KEPT(ret = opusgpu_decoder_ctl(st, request, va_arg(ap, void *)));
+    else CALLER_RAND_KEPT(ret = opusgpu_decoder_ctl(st, request, va_arg(ap, int32_t)));
     va_end(ap);
     return ret;
 }
 
 int opus_decode(OpusDecoder *st, const unsigned char *data, int32_t len, int16_t *pcm, int frame_size, int decode_fec)
 {
-    return opusgpu_decode(st, data, len, pcm, frame_size, decode_fec);
+    /* a lost packet is concealed; so is a request for FEC, which a CELT-only stream cannot carry: libopus runs the PLC
+     * instead (src/opus_decoder.c:608-649) */
+    int ret;
+    if (decode_fec < 0 || decode_fec > 1 || len < 0) return OPUSGPU_BAD_ARG;
+    if (data == NULL || len == 0 || decode_fec) CALLER_RAND_KEPT(ret = opusgpu_decode_lost(st, pcm, frame_size));
+    else CALLER_RAND_KEPT(ret = opusgpu_decode(st, data, len, pcm, frame_size, decode_fec));
+    return ret;
 }
 
-void opus_decoder_destroy(OpusDecoder *st) { opusgpu_decoder_destroy(st); }
+void opus_decoder_destroy(OpusDecoder *st) { CALLER_RAND_KEPT(opusgpu_decoder_destroy(st)); }
 
 const char *opus_strerror(int error) { return opusgpu_strerror(error); }
-const char *opus_get_version_string(void) { return opusgpu_get_version_string(); }
+const char *opus_get_version_string(void)
+{
+    const char *v;
+    CALLER_RAND_KEPT(v = opusgpu_get_version_string());
+    return v;
+}
 
 /* ---- packet helpers: pure functions of the TOC byte (RFC 6716 section 3.1; src/opus.c:169-188,
  * src/opus_decoder.c:944-975, :916-942) ---- */

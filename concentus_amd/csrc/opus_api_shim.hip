@@ -290,3 +290,22 @@ extern "C" int opusgpu_decode(OpusGpuDecoder *st, const unsigned char *data, int
     }
     return ret;
 }
+
+// opus_decode(st, NULL, 0, pcm, frame_size, 0): conceal one lost 20 ms packet (src/opus_decoder.c:611-627)
+extern "C" int opusgpu_decode_lost(OpusGpuDecoder *st, int16_t *pcm, int frame_size)
+{
+    if (!st || !pcm || frame_size <= 0 || frame_size % 120 != 0) return OPUSGPU_BAD_ARG;       // a multiple of 2.5 ms
+    if (frame_size != 960) return OPUSGPU_UNIMPLEMENTED;
+    int32_t ret = 0;
+    int rc = opusgpu_decode_batch_plc(st->d_state, nullptr, 0, nullptr, st->d_pcm, st->d_ret, st->d_rng, 1, st->stream);
+    if (rc < 0) return rc;
+    if (hipMemcpyAsync(&ret, st->d_ret, 4, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
+        hipMemcpyAsync(&st->final_range, st->d_rng, 4, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
+        hipStreamSynchronize(st->stream) != hipSuccess)
+        return OPUSGPU_INTERNAL_ERROR;
+    if (ret > 0) {
+        st->last_packet_duration = ret;
+        if (hipMemcpy(pcm, st->d_pcm, (size_t)ret * 2 * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) return OPUSGPU_INTERNAL_ERROR;
+    }
+    return ret;
+}

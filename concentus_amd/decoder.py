@@ -3,7 +3,7 @@
 The reference decodes one stream at a time: opus_decoder_create() -> opus_decode() per packet
 (opus-fix/include/opus.h:438-462, src/opus_decoder.c:121,758). `OpusDecoderBatch` keeps the same verbs over N
 streams whose state (overlap/history buffer, band energies, post-filter) lives in HBM; all computation happens
-in libopusgpu.so (opusgpu_decode_batch)."""
+in libopusgpu.so (opusgpu_decode_batch; opusgpu_decode_batch_plc when lost packets are to be concealed)."""
 from . import lib as _lib
 
 OPUS_GET_FINAL_RANGE_REQUEST = 4031
@@ -27,9 +27,11 @@ class OpusDecoderBatch:
         _lib.check(_lib.load().opusgpu_celt_dec_state_init(self._states.data_ptr(), self.n, _lib.current_stream_handle()),
                    "opusgpu_celt_dec_state_init")
 
-    def decode(self, packets, lengths):
+    def decode(self, packets, lengths, conceal=False):
         """opus_decode(dec, data, len, pcm, 960, 0) for every stream: packets uint8 [N][stride], lengths int32 [N].
-        Returns (pcm int16 [N][960][2], ret int32 [N] = 960 or a negative error per stream)."""
+        Returns (pcm int16 [N][960][2], ret int32 [N] = 960 or a negative error per stream).
+        conceal=True (opusgpu_decode_batch_plc): a stream with length 0 lost its packet and is concealed
+        (opus_decode(dec, NULL, 0, ...)), as is a one-byte DTX packet; its ret is 960 and its final range 0."""
         import torch
         if packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[0] != self.n or not packets.is_contiguous():
             raise ValueError("packets must be a contiguous uint8 tensor [streams][stride]")
@@ -38,9 +40,24 @@ class OpusDecoderBatch:
         pcm = torch.empty((self.n, 960, 2), dtype=torch.int16, device=packets.device)
         ret = torch.empty((self.n,), dtype=torch.int32, device=packets.device)
         rng = torch.empty((self.n,), dtype=torch.int32, device=packets.device)
-        rc = _lib.load().opusgpu_decode_batch(self._states.data_ptr(), packets.data_ptr(), packets.shape[1], lengths.data_ptr(),
-                                              pcm.data_ptr(), ret.data_ptr(), rng.data_ptr(), self.n, _lib.current_stream_handle())
-        _lib.check(rc, "opusgpu_decode_batch")
+        L = _lib.load()
+        entry = L.opusgpu_decode_batch_plc if conceal else L.opusgpu_decode_batch
+        rc = entry(self._states.data_ptr(), packets.data_ptr(), packets.shape[1], lengths.data_ptr(),
+                   pcm.data_ptr(), ret.data_ptr(), rng.data_ptr(), self.n, _lib.current_stream_handle())
+        _lib.check(rc, "opusgpu_decode_batch_plc" if conceal else "opusgpu_decode_batch")
+        self.final_range = rng
+        return pcm, ret
+
+    def decode_lost(self):
+        """opus_decode(dec, NULL, 0, pcm, 960, 0) for every stream: all of them lost their packet. Returns (pcm, ret) as decode()."""
+        import torch
+        dev = self._states.device
+        pcm = torch.empty((self.n, 960, 2), dtype=torch.int16, device=dev)
+        ret = torch.empty((self.n,), dtype=torch.int32, device=dev)
+        rng = torch.empty((self.n,), dtype=torch.int32, device=dev)
+        rc = _lib.load().opusgpu_decode_batch_plc(self._states.data_ptr(), None, 0, None, pcm.data_ptr(), ret.data_ptr(),
+                                                  rng.data_ptr(), self.n, _lib.current_stream_handle())
+        _lib.check(rc, "opusgpu_decode_batch_plc")
         self.final_range = rng
         return pcm, ret
 

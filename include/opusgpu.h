@@ -58,7 +58,8 @@ int opusgpu_num_cus(void);
 #define OPUSGPU_KERNEL_DEC_LANE       7
 #define OPUSGPU_KERNEL_DEC_SYNTH      8
 #define OPUSGPU_KERNEL_DEC_POST       9
-#define OPUSGPU_KERNEL_COUNT      10
+#define OPUSGPU_KERNEL_DEC_PLC       10    /* the concealment's wave-per-stream kernel (opusgpu_decode_batch_plc) */
+#define OPUSGPU_KERNEL_COUNT      11
 int opusgpu_kernel_timing_enable(int on);
 int opusgpu_kernel_timing_read(double *ms_sum, int *launches, int n_kernels);
 
@@ -168,6 +169,18 @@ int opusgpu_celt_dec_state_size(void);
 int opusgpu_celt_dec_state_init(void *d_states, int n_streams, void *hip_stream);
 int opusgpu_decode_batch(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
                          int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
+/* The same call with packet loss concealment (celt_decode_lost, celt/celt_decoder.c:395-711, bit-exact): the arguments of
+ * opusgpu_decode_batch, and
+ *   d_len[i] == 0                  stream i lost its packet: opus_decode(st, NULL, 0, pcm, 960, 0);
+ *   d_len[i] == 1 with TOC 0xFC    DTX, concealed in the same way (src/opus_decoder.c:246-251); other one-byte packets
+ *                                  return OPUSGPU_UNIMPLEMENTED;
+ *   d_len == NULL                  every stream is lost; d_packets may then be NULL.
+ * A concealed stream reports d_ret = 960 and d_rng = 0; one that has not decoded a packet yet gets 960 zero samples and keeps
+ * its state. The first five losses in a row extrapolate the last pitch period, later ones decay into noise at the background
+ * energy. A received stream behaves exactly as in opusgpu_decode_batch, and streams rejected per stream are left alone.
+ * One more launch than opusgpu_decode_batch (four); asynchronous on hip_stream, no allocation, no synchronisation inside. */
+int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                             int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
 
 /* ---- libopus single-stream encoder API as a batch of one (plumbing; BASELINE config #1) --------------
  * Same verbs, argument meaning and return codes as opus_encoder_create / opus_encoder_ctl / opus_encode /
@@ -183,11 +196,15 @@ int32_t opusgpu_encode(OpusGpuEncoder *st, const int16_t *pcm, int frame_size, u
 void opusgpu_encoder_destroy(OpusGpuEncoder *st);
 /* Decoder side, likewise: opus_decoder_create / opus_decode / opus_decoder_ctl / opus_decoder_destroy
  * (opus-fix/include/opus.h:438-505; src/opus_decoder.c:121, :758, :788, :911) for 48 kHz stereo and CELT-only
- * 20 ms stereo packets; ctl: OPUS_GET_FINAL_RANGE, OPUS_RESET_STATE. data == NULL / decode_fec (loss concealment)
- * return OPUS_UNIMPLEMENTED. */
+ * 20 ms stereo packets; ctl: OPUS_GET_FINAL_RANGE, OPUS_GET_LAST_PACKET_DURATION, OPUS_RESET_STATE. opusgpu_decode itself
+ * returns OPUS_UNIMPLEMENTED for data == NULL / decode_fec; a lost packet goes through opusgpu_decode_lost, which is
+ * opus_decode(st, NULL, 0, pcm, frame_size, 0): 960 for frame_size 960 (afterwards the last packet duration is 960 and the
+ * final range 0), OPUS_UNIMPLEMENTED for any other multiple of 120, OPUS_BAD_ARG otherwise. The libopus-named opus_decode of
+ * compat/libopus.so routes lost packets and decode_fec there. */
 typedef struct OpusGpuDecoder OpusGpuDecoder;
 OpusGpuDecoder *opusgpu_decoder_create(int32_t Fs, int channels, int *error);
 int opusgpu_decode(OpusGpuDecoder *st, const unsigned char *data, int32_t len, int16_t *pcm, int frame_size, int decode_fec);
+int opusgpu_decode_lost(OpusGpuDecoder *st, int16_t *pcm, int frame_size);
 int opusgpu_decoder_ctl(OpusGpuDecoder *st, int request, ...);
 void opusgpu_decoder_destroy(OpusGpuDecoder *st);
 
