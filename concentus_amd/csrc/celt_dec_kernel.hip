@@ -14,7 +14,7 @@
 #define CA_LANE_FRAME 1
 #include "celt_lane_tables.h"
 #include "celt_plc.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"                 // opusgpu_qab_dec_record: this unit holds the decode side of the quant_all_bands hook
 
 namespace ca {
 
@@ -182,17 +182,13 @@ __global__ __launch_bounds__(64) void quant_all_bands_dec_hook_kernel(opusgpu_qa
     for (int k = 0; k < 2 * NB; k++) F.collapse_masks[k] = 0;
     RangeDec dec;
     dec.buf = rec->buf;
-    dec.storage = rec->ec_storage; dec.end_offs = rec->ec_end_offs; dec.end_window = rec->ec_end_window;
-    dec.nend_bits = rec->ec_nend_bits; dec.nbits_total = rec->ec_nbits_total; dec.offs = rec->ec_offs; dec.rng = rec->ec_rng;
-    dec.val = rec->ec_val; dec.ext = rec->ec_ext; dec.rem = rec->ec_rem; dec.error = rec->ec_error;
+    load(dec, rec->ec);
     u32 seed = rec->seed;
     quant_all_bands_dec(F, dec, rec->shortBlocks, rec->spread, rec->dual_stereo, rec->intensity, rec->total_bits, rec->balance,
                         rec->codedBands, &seed);
     for (int k = 0; k < 2 * NB; k++) rec->collapse_masks[k] = F.collapse_masks[k];
     rec->seed = seed;
-    rec->ec_end_offs = dec.end_offs; rec->ec_end_window = dec.end_window; rec->ec_nend_bits = dec.nend_bits;
-    rec->ec_nbits_total = dec.nbits_total; rec->ec_offs = dec.offs; rec->ec_rng = dec.rng; rec->ec_val = dec.val;
-    rec->ec_ext = dec.ext; rec->ec_rem = dec.rem; rec->ec_error = dec.error;
+    store(rec->ec, dec);
 }
 
 }  // namespace ca
@@ -216,6 +212,40 @@ extern "C" int opusgpu_celt_dec_state_init(void *d_states, int n_streams, void *
     return opusgpu_check_launch();
 }
 
+extern "C" void opusgpu_launch_dec_plc(void *states, int n, hipStream_t s);
+
+// The pipeline of both batched entry points, arguments checked: the lane kernel, with PLC the concealment's wave-per-stream kernel
+// (it leaves at once on a received stream), the synthesis, and the post kernel of the matching kind; each in its timing bracket.
+template <bool PLC>
+static int decode_batch_launch(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len, int16_t *d_pcm,
+                               int32_t *d_ret, uint32_t *d_rng, int n_streams, hipStream_t s)
+{
+    int slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_LANE, s);
+    {
+        const int a = opusgpu_lane_frames(32);          // (decoder lane kernel: 5.06 ms at 32 streams per wavefront, 5.39 ms at 64)
+        const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
+#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, PLC>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
+                                        d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
+        if (a == 32) CA_LAUNCH(32);
+        else CA_LAUNCH(64);
+#undef CA_LAUNCH
+    }
+    opusgpu_timing_end(slot, s);
+    if (PLC) {
+        slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_PLC, s);
+        opusgpu_launch_dec_plc(d_states, n_streams, s);
+        opusgpu_timing_end(slot, s);
+    }
+    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_SYNTH, s);
+    opusgpu_launch_dec_synth(d_states, n_streams, s);
+    opusgpu_timing_end(slot, s);
+    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
+    const auto post = PLC ? ca::celt_decode_post_plc_kernel : ca::celt_decode_post_kernel;
+    hipLaunchKernelGGL(post, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s, (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
+    opusgpu_timing_end(slot, s);
+    return opusgpu_check_launch();
+}
+
 extern "C" int opusgpu_decode_batch(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
                                     int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *stream)
 {
@@ -223,32 +253,10 @@ extern "C" int opusgpu_decode_batch(void *d_states, const unsigned char *d_packe
     if (n_streams == 0) return OPUSGPU_OK;
     if (!d_states || !d_packets || !d_len || !d_pcm || !d_ret || !d_rng || packet_stride <= 0) return OPUSGPU_BAD_ARG;
     if (((uintptr_t)d_pcm & 15) != 0) return OPUSGPU_BAD_ARG;         // the post kernel stores 16 bytes at a time
-    hipStream_t s = (hipStream_t)stream;
-    int slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_LANE, s);
-    {
-        const int a = opusgpu_lane_frames(32);          // (decoder lane kernel: 5.06 ms at 32 streams per wavefront, 5.39 ms at 64)
-        const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
-#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, false>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
-                                        d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
-        if (a == 32) CA_LAUNCH(32);
-        else CA_LAUNCH(64);
-#undef CA_LAUNCH
-    }
-    opusgpu_timing_end(slot, s);
-    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_SYNTH, s);
-    opusgpu_launch_dec_synth(d_states, n_streams, s);
-    opusgpu_timing_end(slot, s);
-    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
-    hipLaunchKernelGGL(ca::celt_decode_post_kernel, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s,
-                       (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
-    opusgpu_timing_end(slot, s);
-    return opusgpu_check_launch();
+    return decode_batch_launch<false>(d_states, d_packets, packet_stride, d_len, d_pcm, d_ret, d_rng, n_streams, (hipStream_t)stream);
 }
 
-extern "C" void opusgpu_launch_dec_plc(void *states, int n, hipStream_t s);
-
-// opusgpu_decode_batch with packet loss concealment: the same lane and synthesis kernels, the concealment's wave-per-stream kernel
-// between them (it leaves at once on a received stream) and the post kernel that knows about concealed streams
+// opusgpu_decode_batch with packet loss concealment (the post kernel knows about concealed streams)
 extern "C" int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
                                         int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *stream)
 {
@@ -258,27 +266,5 @@ extern "C" int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_p
     if (d_len && (!d_packets || packet_stride <= 0)) return OPUSGPU_BAD_ARG;     // d_len == NULL: every stream is lost, no packets
     if (((uintptr_t)d_pcm & 15) != 0) return OPUSGPU_BAD_ARG;
     if (!d_len) { d_packets = nullptr; packet_stride = 0; }
-    hipStream_t s = (hipStream_t)stream;
-    int slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_LANE, s);
-    {
-        const int a = opusgpu_lane_frames(32);
-        const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
-#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, true>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
-                                        d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
-        if (a == 32) CA_LAUNCH(32);
-        else CA_LAUNCH(64);
-#undef CA_LAUNCH
-    }
-    opusgpu_timing_end(slot, s);
-    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_PLC, s);
-    opusgpu_launch_dec_plc(d_states, n_streams, s);
-    opusgpu_timing_end(slot, s);
-    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_SYNTH, s);
-    opusgpu_launch_dec_synth(d_states, n_streams, s);
-    opusgpu_timing_end(slot, s);
-    slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
-    hipLaunchKernelGGL(ca::celt_decode_post_plc_kernel, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s,
-                       (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
-    opusgpu_timing_end(slot, s);
-    return opusgpu_check_launch();
+    return decode_batch_launch<true>(d_states, d_packets, packet_stride, d_len, d_pcm, d_ret, d_rng, n_streams, (hipStream_t)stream);
 }

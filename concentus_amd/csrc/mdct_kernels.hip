@@ -7,9 +7,9 @@
 //
 // Replaces clt_mdct_forward_c / clt_mdct_backward_c (opus-fix/celt/mdct.c:121,263) as driven by
 // compute_mdcts (celt/celt_encoder.c:418-461) and celt_synthesis (celt/celt_decoder.c:323-346).
+// The per-call hooks at the end (opus_fft, clt_mdct_forward / _backward) take their host steps from hook_host.h.
 #include "mdct_dev.h"
-#include "opusgpu_internal.h"
-#include <stdlib.h>
+#include "hook_host.h"
 
 namespace ca {
 
@@ -172,50 +172,31 @@ extern "C" int opusgpu_fft_batch(const int32_t *d_fin, int32_t *d_fout, int n_tr
     const int grid = grid_for(n_transforms, 12);
     const int2 *fin = (const int2 *)d_fin;
     int2 *fout = (int2 *)d_fout;
-    switch (shift) {
-    case 0: hipLaunchKernelGGL(fft_kernel<0>, dim3(grid), dim3(64), 0, s, fin, fout, n_transforms); break;
-    case 1: hipLaunchKernelGGL(fft_kernel<1>, dim3(grid), dim3(64), 0, s, fin, fout, n_transforms); break;
-    case 2: hipLaunchKernelGGL(fft_kernel<2>, dim3(grid), dim3(64), 0, s, fin, fout, n_transforms); break;
-    default: hipLaunchKernelGGL(fft_kernel<3>, dim3(grid), dim3(64), 0, s, fin, fout, n_transforms); break;
-    }
+    for_shift(shift, [&](auto S) { hipLaunchKernelGGL(fft_kernel<decltype(S)::value>, dim3(grid), dim3(64), 0, s, fin, fout, n_transforms); });
     return opusgpu_check_launch();
 }
 
 // opus_fft(cfg, fin, fout) with the reference's argument list (macro at celt/kiss_fft.h:135-178 -> opus_fft_c): host
 // pointers, one transform, synchronous. `cfg` must be one of the four states of the static 48 kHz mode
-// (nfft 480 / 240 / 120 / 60, scale 17476, scale_shift 8 - shift); the head of kiss_fft_state is validated, its
-// tables are not read. Plumbing / parity only.
-struct ref_kiss_fft_state_head { int nfft; int16_t scale; int scale_shift; int shift; };
-
+// (nfft 480 / 240 / 120 / 60, scale 17476, scale_shift 8 - shift); the head of kiss_fft_state is validated
+// (kiss_fft_shift, hook_host.h), its tables are not read. Plumbing / parity only.
 extern "C" void opusgpu_opus_fft(const void *cfg, const void *fin, void *fout)
 {
-    const ref_kiss_fft_state_head *h = (const ref_kiss_fft_state_head *)cfg;
-    int shift = -1;
-    if (h && fin && fout && fin != fout)
-        for (int k = 0; k < 4; k++)
-            if (h->nfft == (480 >> k) && h->scale == 17476 && h->scale_shift == 8 - k) shift = k;
-    if (shift < 0) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    const int shift = fin && fout && fin != fout ? kiss_fft_shift(cfg) : -1;
+    if (shift < 0) { fail(OPUSGPU_BAD_ARG); return; }
     const size_t bytes = (size_t)(480 >> shift) * 8;
-    int32_t *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc(&d_in, bytes) != hipSuccess || hipMalloc(&d_out, bytes) != hipSuccess) {
-        opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL);
-        if (d_in) (void)hipFree(d_in);
-        return;
-    }
-    int rc = opusgpu_copy(d_in, fin, bytes, hipMemcpyHostToDevice);
-    if (rc == OPUSGPU_OK) rc = opusgpu_fft_batch(d_in, d_out, 1, shift, nullptr);
-    if (rc == OPUSGPU_OK) rc = opusgpu_copy(fout, d_out, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    opusgpu_set_last_error(rc);
+    DevBuf din(bytes), dout(bytes);
+    int rc = allocated(din, dout);
+    if (rc == OPUSGPU_OK) rc = h2d(din.p, fin, bytes);
+    if (rc == OPUSGPU_OK) rc = opusgpu_fft_batch((const int32_t *)din.p, (int32_t *)dout.p, 1, shift, nullptr);
+    if (rc == OPUSGPU_OK) rc = d2h(fout, dout.p, bytes);
+    fail(rc);
 }
 
 // ---- per-call hooks with the reference's own signature (host pointers) ---------------------------
 // Same argument list as clt_mdct_forward_c / clt_mdct_backward_c (celt/mdct.h:77-110). `l`, `window`
 // and `overlap` must describe the static mode (n = 1920, window120, 120); they are validated, not read
 // on the device. Latency-dominated: for plumbing/parity only, throughput comes from the batch API.
-struct ref_mdct_lookup_head { int n; int maxshift; };
-
 static int hook_args_ok(const void *l, const void *window, int overlap, int shift, int stride)
 {
     if (!l || !window || overlap != 120 || shift < 0 || shift > 3 || stride < 1) return 0;
@@ -223,58 +204,41 @@ static int hook_args_ok(const void *l, const void *window, int overlap, int shif
     return h->n == 1920 && h->maxshift == 3;
 }
 
+// One transform from `in` into `out`. `out` is live on entry (forward: the gaps of a strided output; backward: the previous
+// frame's tail), so it is copied in as well. launch(S, d_in, d_out) launches the <SHIFT> instance, SHIFT = decltype(S)::value.
+template <class Launch>
+static void mdct_hook_run(const int32_t *in, size_t in_bytes, int32_t *out, size_t out_bytes, int shift, Launch launch)
+{
+    DevBuf din(in_bytes), dout(out_bytes);
+    int rc = allocated(din, dout);
+    if (rc == OPUSGPU_OK) rc = h2d(din.p, in, in_bytes);
+    if (rc == OPUSGPU_OK) rc = h2d(dout.p, out, out_bytes);
+    if (rc == OPUSGPU_OK) {
+        for_shift(shift, [&](auto S) { launch(S, (const i32 *)din.p, (i32 *)dout.p); });
+        rc = opusgpu_check_launch();
+    }
+    if (rc == OPUSGPU_OK) rc = d2h(out, dout.p, out_bytes);
+    fail(rc);
+}
+
 extern "C" void opusgpu_clt_mdct_forward(const void *l, int32_t *in, int32_t *out, const int16_t *window,
                                          int overlap, int shift, int stride, int arch)
 {
     (void)arch;
-    if (!hook_args_ok(l, window, overlap, shift, stride)) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!hook_args_ok(l, window, overlap, shift, stride)) { fail(OPUSGPU_BAD_ARG); return; }
     const int n2 = 960 >> shift;
-    const size_t in_bytes = (size_t)(n2 + 120) * 4, out_elems = (size_t)(n2 - 1) * stride + 1;
-    int32_t *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc(&d_in, in_bytes) != hipSuccess || hipMalloc(&d_out, out_elems * 4) != hipSuccess) {
-        opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL);
-        if (d_in) (void)hipFree(d_in);
-        return;
-    }
-    int rc = opusgpu_copy(d_in, in, in_bytes, hipMemcpyHostToDevice);
-    if (rc == OPUSGPU_OK) rc = opusgpu_copy(d_out, out, out_elems * 4, hipMemcpyHostToDevice);   // keep the gaps when stride > 1
-    if (rc == OPUSGPU_OK) switch (shift) {
-    case 0: hipLaunchKernelGGL(mdct_forward_single_kernel<0>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    case 1: hipLaunchKernelGGL(mdct_forward_single_kernel<1>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    case 2: hipLaunchKernelGGL(mdct_forward_single_kernel<2>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    default: hipLaunchKernelGGL(mdct_forward_single_kernel<3>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    }
-    if (rc == OPUSGPU_OK) rc = opusgpu_check_launch();
-    if (rc == OPUSGPU_OK) rc = opusgpu_copy(out, d_out, out_elems * 4, hipMemcpyDeviceToHost);
-    opusgpu_set_last_error(rc);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    mdct_hook_run(in, (size_t)(n2 + 120) * 4, out, ((size_t)(n2 - 1) * stride + 1) * 4, shift, [&](auto S, const i32 *d_in, i32 *d_out) {
+        hipLaunchKernelGGL(mdct_forward_single_kernel<decltype(S)::value>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride);
+    });
 }
 
 extern "C" void opusgpu_clt_mdct_backward(const void *l, int32_t *in, int32_t *out, const int16_t *window,
                                           int overlap, int shift, int stride, int arch)
 {
     (void)arch;
-    if (!hook_args_ok(l, window, overlap, shift, stride)) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!hook_args_ok(l, window, overlap, shift, stride)) { fail(OPUSGPU_BAD_ARG); return; }
     const int n2 = 960 >> shift;
-    const size_t in_elems = (size_t)(n2 - 1) * stride + 1, out_bytes = (size_t)(n2 + 120) * 4;
-    int32_t *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc(&d_in, in_elems * 4) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess) {
-        opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL);
-        if (d_in) (void)hipFree(d_in);
-        return;
-    }
-    int rc = opusgpu_copy(d_in, in, in_elems * 4, hipMemcpyHostToDevice);
-    if (rc == OPUSGPU_OK) rc = opusgpu_copy(d_out, out, out_bytes, hipMemcpyHostToDevice);
-    if (rc == OPUSGPU_OK) switch (shift) {
-    case 0: hipLaunchKernelGGL(mdct_backward_single_kernel<0>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    case 1: hipLaunchKernelGGL(mdct_backward_single_kernel<1>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    case 2: hipLaunchKernelGGL(mdct_backward_single_kernel<2>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    default: hipLaunchKernelGGL(mdct_backward_single_kernel<3>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride); break;
-    }
-    if (rc == OPUSGPU_OK) rc = opusgpu_check_launch();
-    if (rc == OPUSGPU_OK) rc = opusgpu_copy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
-    opusgpu_set_last_error(rc);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    mdct_hook_run(in, ((size_t)(n2 - 1) * stride + 1) * 4, out, (size_t)(n2 + 120) * 4, shift, [&](auto S, const i32 *d_in, i32 *d_out) {
+        hipLaunchKernelGGL(mdct_backward_single_kernel<decltype(S)::value>, dim3(1), dim3(64), 0, 0, d_in, d_out, stride);
+    });
 }

@@ -15,15 +15,6 @@ extern "C" int opusgpu_lane_frames(int dflt);
 extern "C" int *opusgpu_bad_record_counter(void);
 extern "C" int opusgpu_private_bad_counter_begin(void);
 extern "C" int opusgpu_private_bad_counter_end(void);
-// Scope of a one-record hook: the record kernels it launches count rejected records into a counter of the calling thread
-// (runtime.hip), never into the device's shared one that concurrent batch callers read through opusgpu_silk_bad_records().
-struct OpusgpuHookBadScope {
-    int rc;
-    bool open;
-    OpusgpuHookBadScope() : rc(opusgpu_private_bad_counter_begin()), open(true) {}
-    int take() { open = false; return opusgpu_private_bad_counter_end(); }
-    ~OpusgpuHookBadScope() { if (open) (void)opusgpu_private_bad_counter_end(); }
-};
 // Argument checks of opusgpu_encode_batch: the configuration inside the supported region, pointers, strides, workspace. Returns an
 // error code, or OPUSGPU_OK with *chunk = frames per pass of the pipeline (what the workspace holds; 0 when n_frames == 0: nothing
 // to do) and *in_ws = the time-signal rows of the workspace, which follow its chunk FrameMid records.
@@ -42,24 +33,3 @@ extern "C" void opusgpu_launch_back_lane(const opusgpu_celt_config *cfg, void *s
 // silk_nlsf_kernels.hip). They are bound by the latency of one record's serial chain, not by issue slots, so partially filled
 // wavefronts (16 or 32 records: more wavefronts per SIMD) were swept against the full one (64), which is what ships.
 enum { SILK_LANES_PER_BLOCK = 64 };
-// hipMemcpy of a per-call hook with its status mapped: OPUSGPU_OK or OPUSGPU_INTERNAL_ERROR
-static inline int opusgpu_copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
-{
-    return hipMemcpy(dst, src, bytes, kind) == hipSuccess ? OPUSGPU_OK : OPUSGPU_INTERNAL_ERROR;
-}
-
-// quant_all_bands(encode = 0) as a per-call hook: the record the host entry (quant_bands_hook.hip) hands to the decoder's lane
-// build (celt_dec_kernel.hip), and the launcher. In: pulses, tf_res, the scalars, seed, the range decoder's fields + the packet
-// bytes; out: X (both channels), collapse_masks, seed, the decoder's fields.
-struct opusgpu_qab_dec_record {
-    int16_t X[2 * 960];
-    int16_t norm[2 * 624];             // working storage (the folding source), not an output
-    int32_t pulses[21], tf_res[21];
-    int32_t shortBlocks, spread, dual_stereo, intensity, total_bits, balance, codedBands;
-    uint32_t seed;
-    uint32_t ec_storage, ec_end_offs, ec_end_window, ec_offs, ec_rng, ec_val, ec_ext;
-    int32_t ec_nend_bits, ec_nbits_total, ec_rem, ec_error, pad;
-    unsigned char collapse_masks[2 * 21 + 6];
-    unsigned char buf[1280];
-};
-extern "C" int opusgpu_launch_quant_all_bands_dec(opusgpu_qab_dec_record *d_rec);

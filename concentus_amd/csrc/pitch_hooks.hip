@@ -7,7 +7,7 @@
 // this entry point exists so the reference's RTCD slot has a target, for plumbing and parity. One lane per lag, x
 // staged in LDS, the maximum by a wave reduction and one atomic per wavefront.
 #include "fixmath.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 
 namespace ca {
 
@@ -36,33 +36,20 @@ __global__ __launch_bounds__(256) void pitch_xcorr_kernel(const i16 *__restrict_
 extern "C" int32_t opusgpu_celt_pitch_xcorr(const int16_t *x, const int16_t *y, int32_t *xcorr, int len, int max_pitch, int arch)
 {
     (void)arch;
-    if (!x || !y || !xcorr || len < 1 || len > ca::XCORR_MAX_LEN || max_pitch < 1) {
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
-        return 0;
-    }
+    if (!x || !y || !xcorr || len < 1 || len > ca::XCORR_MAX_LEN || max_pitch < 1) { fail(OPUSGPU_BAD_ARG); return 0; }
     const size_t xb = (size_t)len * 2, yb = (size_t)(len + max_pitch - 1) * 2, cb = (size_t)max_pitch * 4;
-    int16_t *d_x = nullptr, *d_y = nullptr;
-    int32_t *d_c = nullptr, *d_m = nullptr, h_m = 1;
-    int rc = OPUSGPU_OK;
-    if (hipMalloc(&d_x, xb) != hipSuccess || hipMalloc(&d_y, yb) != hipSuccess || hipMalloc(&d_c, cb) != hipSuccess ||
-        hipMalloc(&d_m, 4) != hipSuccess)
-        rc = OPUSGPU_ALLOC_FAIL;
+    int32_t h_m = 1;                                                                           // maxcorr starts at 1 (pitch.c:224)
+    DevBuf dx(xb), dy(yb), dc(cb), dm(4);
+    int rc = allocated(dx, dy, dc, dm);
+    if (rc == OPUSGPU_OK) rc = h2d(dx.p, x, xb);
+    if (rc == OPUSGPU_OK) rc = h2d(dy.p, y, yb);
+    if (rc == OPUSGPU_OK) rc = h2d(dm.p, &h_m, 4);
     if (rc == OPUSGPU_OK) {
-        rc = opusgpu_copy(d_x, x, xb, hipMemcpyHostToDevice);
-        if (rc == OPUSGPU_OK) rc = opusgpu_copy(d_y, y, yb, hipMemcpyHostToDevice);
-        if (rc == OPUSGPU_OK) rc = opusgpu_copy(d_m, &h_m, 4, hipMemcpyHostToDevice);         // maxcorr starts at 1 (pitch.c:224)
-        if (rc == OPUSGPU_OK) {
-            hipLaunchKernelGGL(ca::pitch_xcorr_kernel, dim3((max_pitch + 255) / 256), dim3(256), 0, 0, d_x, d_y, d_c, len, max_pitch, d_m);
-            rc = opusgpu_check_launch();
-        }
-        if (rc == OPUSGPU_OK && (hipMemcpy(xcorr, d_c, cb, hipMemcpyDeviceToHost) != hipSuccess ||
-                                 hipMemcpy(&h_m, d_m, 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = OPUSGPU_INTERNAL_ERROR;
+        hipLaunchKernelGGL(ca::pitch_xcorr_kernel, dim3((max_pitch + 255) / 256), dim3(256), 0, 0, (const ca::i16 *)dx.p, (const ca::i16 *)dy.p,
+                           (ca::i32 *)dc.p, len, max_pitch, (ca::i32 *)dm.p);
+        rc = opusgpu_check_launch();
     }
-    if (d_x) (void)hipFree(d_x);
-    if (d_y) (void)hipFree(d_y);
-    if (d_c) (void)hipFree(d_c);
-    if (d_m) (void)hipFree(d_m);
-    opusgpu_set_last_error(rc);
-    return rc == OPUSGPU_OK ? h_m : 0;
+    if (rc == OPUSGPU_OK) rc = d2h(xcorr, dc.p, cb);
+    if (rc == OPUSGPU_OK) rc = d2h(&h_m, dm.p, 4);
+    return fail(rc) == OPUSGPU_OK ? h_m : 0;
 }

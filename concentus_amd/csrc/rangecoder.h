@@ -29,6 +29,26 @@ struct RangeEnc {
     int error;
 };
 
+// The coder's eleven scalars (encoder or decoder) as they travel in the records of the per-call hooks; the host side fills them
+// from the reference's ec_ctx and writes them back (hook_host.h).
+struct EcFields {
+    u32 storage, end_offs, end_window, offs, rng, val, ext;
+    i32 nend_bits, nbits_total, rem, error;
+};
+
+CA_DEV void load(RangeEnc &e, const EcFields &f)                       // wave-uniform reads: every lane holds the same state
+{
+    e.storage = uni(f.storage); e.end_offs = uni(f.end_offs); e.end_window = uni(f.end_window); e.offs = uni(f.offs);
+    e.rng = uni(f.rng); e.val = uni(f.val); e.ext = uni(f.ext); e.nend_bits = uni(f.nend_bits);
+    e.nbits_total = uni(f.nbits_total); e.rem = uni(f.rem); e.error = uni(f.error);
+}
+
+CA_DEV void store(EcFields &f, const RangeEnc &e)
+{
+    f.storage = e.storage; f.end_offs = e.end_offs; f.end_window = e.end_window; f.offs = e.offs; f.rng = e.rng; f.val = e.val;
+    f.ext = e.ext; f.nend_bits = e.nend_bits; f.nbits_total = e.nbits_total; f.rem = e.rem; f.error = e.error;
+}
+
 CA_DEV void ec_enc_init(RangeEnc &e, u8 *buf, u32 size)               // entenc.c:163-184
 {
     e.buf = buf;

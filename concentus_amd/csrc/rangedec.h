@@ -20,6 +20,18 @@ struct RangeDec {
     int error;
 };
 
+CA_DEV void load(RangeDec &d, const EcFields &f)                       // the hook records' scalars (rangecoder.h); buf is the caller's
+{
+    d.storage = f.storage; d.end_offs = f.end_offs; d.end_window = f.end_window; d.offs = f.offs; d.rng = f.rng; d.val = f.val;
+    d.ext = f.ext; d.nend_bits = f.nend_bits; d.nbits_total = f.nbits_total; d.rem = f.rem; d.error = f.error;
+}
+
+CA_DEV void store(EcFields &f, const RangeDec &d)
+{
+    f.storage = d.storage; f.end_offs = d.end_offs; f.end_window = d.end_window; f.offs = d.offs; f.rng = d.rng; f.val = d.val;
+    f.ext = d.ext; f.nend_bits = d.nend_bits; f.nbits_total = d.nbits_total; f.rem = d.rem; f.error = d.error;
+}
+
 CA_DEV int ec_read_byte(RangeDec &d) { return d.offs < d.storage ? d.buf[d.offs++] : 0; }                    // entdec.c:93
 CA_DEV int ec_read_byte_from_end(RangeDec &d) { return d.end_offs < d.storage ? d.buf[d.storage - ++d.end_offs] : 0; }
 

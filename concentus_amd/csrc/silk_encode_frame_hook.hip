@@ -6,43 +6,18 @@
 // with memcpy / assignments: buffer shifts, the state copies of the loop, the fields carried to the next frame.
 // One record per launch: plumbing / parity (a reference encoder linked against these emits the reference's packets,
 // tests/test_hooks_gpu.py); throughput is the business of the batched entry points.
-#include <stdlib.h>
-#include <string.h>
-#include <hip/hip_runtime.h>
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 #include "../../include/opusgpu_silk.h"
 #include "../../include/opusgpu_hooks.h"
 
 namespace {
 
-int rd_int(const void *base, int off) { int v; memcpy(&v, (const char *)base + off, sizeof(v)); return v; }
-void wr_int(void *base, int off, int v) { memcpy((char *)base + off, &v, sizeof(v)); }
-int16_t rd_i16(const void *base, int off) { int16_t v; memcpy(&v, (const char *)base + off, sizeof(v)); return v; }
-void wr_i16(void *base, int off, int16_t v) { memcpy((char *)base + off, &v, sizeof(v)); }
-
-// the tree's ec_ctx, x86-64 (celt/entcode.h:63-94, with the trailing EC_DIFF of this tree)
-struct ref_ec_ctx {
-    unsigned char *buf;
-    uint32_t storage, end_offs, end_window;
-    int nend_bits, nbits_total;
-    uint32_t offs, rng, val, ext;
-    int rem, error, EC_DIFF;
-};
-
-struct DevMem {
-    void *p = nullptr;
-    explicit DevMem(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) p = nullptr; }
-    ~DevMem() { if (p) (void)hipFree(p); }
-    DevMem(const DevMem &) = delete;
-    DevMem &operator=(const DevMem &) = delete;
-};
-
+// the coder as the public record of the bits kernel: the scalars, the head bytes [0, offs) and the tail bytes [storage - end_offs, storage)
 bool ec_to_record(opusgpu_ec_state *d, const ref_ec_ctx *e)
 {
     if (!e->buf || e->storage > OPUSGPU_EC_BUF || e->offs > e->storage || e->end_offs > e->storage) return false;
     memset(d, 0, sizeof(*d));
-    d->storage = e->storage; d->end_offs = e->end_offs; d->end_window = e->end_window; d->nend_bits = e->nend_bits; d->nbits_total = e->nbits_total;
-    d->offs = e->offs; d->rng = e->rng; d->val = e->val; d->ext = e->ext; d->rem = e->rem; d->error = e->error;
+    ec_copy_fields(*d, *e);
     memcpy(d->buf, e->buf, e->offs);
     memcpy(d->buf + e->storage - e->end_offs, e->buf + e->storage - e->end_offs, e->end_offs);
     return true;
@@ -50,8 +25,9 @@ bool ec_to_record(opusgpu_ec_state *d, const ref_ec_ctx *e)
 
 void ec_from_record(ref_ec_ctx *e, const opusgpu_ec_state *d)
 {
-    e->end_offs = d->end_offs; e->end_window = d->end_window; e->nend_bits = d->nend_bits; e->nbits_total = d->nbits_total;
-    e->offs = d->offs; e->rng = d->rng; e->val = d->val; e->ext = d->ext; e->rem = d->rem; e->error = d->error;
+    ca::EcFields f;
+    ec_copy_fields(f, *d);
+    ec_fields_to(e, f);
     memcpy(e->buf, d->buf, d->offs);
     memcpy(e->buf + e->storage - d->end_offs, d->buf + d->storage - d->end_offs, d->end_offs);
 }
@@ -59,42 +35,30 @@ void ec_from_record(ref_ec_ctx *e, const opusgpu_ec_state *d)
 // one opusgpu_silk_bits_in record on the coder `e`
 int run_bits(const opusgpu_silk_bits_in &in, ref_ec_ctx *e, opusgpu_silk_bits_out *out)
 {
-    opusgpu_ec_state *h_ec = (opusgpu_ec_state *)malloc(sizeof(*h_ec));
-    if (!h_ec) return OPUSGPU_ALLOC_FAIL;
-    OpusgpuHookBadScope bad;                 // rejected records count into this thread's counter, not the device's shared one
-    int rc = ec_to_record(h_ec, e) ? bad.rc : OPUSGPU_BAD_ARG;
-    DevMem din(sizeof(in)), dec(sizeof(*h_ec)), dout(sizeof(*out));
-    if (rc == OPUSGPU_OK && (!din.p || !dec.p || !dout.p)) rc = OPUSGPU_ALLOC_FAIL;
-    if (rc == OPUSGPU_OK && (hipMemcpy(din.p, &in, sizeof(in), hipMemcpyHostToDevice) != hipSuccess ||
-                             hipMemcpy(dec.p, h_ec, sizeof(*h_ec), hipMemcpyHostToDevice) != hipSuccess))
-        rc = OPUSGPU_INTERNAL_ERROR;
-    if (rc == OPUSGPU_OK)
-        rc = opusgpu_silk_encode_bits_batch((const opusgpu_silk_bits_in *)din.p, (opusgpu_ec_state *)dec.p, (opusgpu_silk_bits_out *)dout.p, 1, nullptr);
-    if (rc == OPUSGPU_OK && (hipMemcpy(out, dout.p, sizeof(*out), hipMemcpyDeviceToHost) != hipSuccess ||
-                             hipMemcpy(h_ec, dec.p, sizeof(*h_ec), hipMemcpyDeviceToHost) != hipSuccess))
-        rc = OPUSGPU_INTERNAL_ERROR;
-    if (rc == OPUSGPU_OK && out->status != OPUSGPU_OK) rc = out->status;
-    if (rc == OPUSGPU_OK) ec_from_record(e, h_ec);
-    free(h_ec);
+    HeapRec<opusgpu_ec_state> h_ec;
+    if (!h_ec.p) return OPUSGPU_ALLOC_FAIL;
+    if (!ec_to_record(h_ec.p, e)) return OPUSGPU_BAD_ARG;
+    const int rc = run_record(&in, out, h_ec.p, [](const opusgpu_silk_bits_in *i, opusgpu_ec_state *s, opusgpu_silk_bits_out *o) {
+        return opusgpu_silk_encode_bits_batch(i, s, o, 1, nullptr);
+    });
+    if (rc == OPUSGPU_OK) ec_from_record(e, h_ec.p);
     return rc;
 }
 
-// one step of the bitrate loop on the device: the record + the coder's ec_tell() words
+// one step of the bitrate loop on the device: the record (in and out, it carries the status) + the coder's ec_tell() words
 int run_rate_step(opusgpu_silk_rate_ctl *ctl, const ref_ec_ctx *e)
 {
-    opusgpu_ec_state *h_ec = (opusgpu_ec_state *)calloc(1, sizeof(*h_ec));
-    if (!h_ec) return OPUSGPU_ALLOC_FAIL;
+    HeapRec<opusgpu_ec_state> h_ec;
+    if (!h_ec.p) return OPUSGPU_ALLOC_FAIL;
     h_ec->storage = e->storage; h_ec->nbits_total = e->nbits_total; h_ec->rng = e->rng; h_ec->offs = e->offs;
-    DevMem dctl(sizeof(*ctl)), dec(sizeof(*h_ec));
     OpusgpuHookBadScope bad;                 // rejected records count into this thread's counter, not the device's shared one
-    int rc = (dctl.p && dec.p) ? bad.rc : OPUSGPU_ALLOC_FAIL;
-    if (rc == OPUSGPU_OK && (hipMemcpy(dctl.p, ctl, sizeof(*ctl), hipMemcpyHostToDevice) != hipSuccess ||
-                             hipMemcpy(dec.p, h_ec, sizeof(*h_ec), hipMemcpyHostToDevice) != hipSuccess))
-        rc = OPUSGPU_INTERNAL_ERROR;
-    if (rc == OPUSGPU_OK) rc = opusgpu_silk_rate_control_batch((opusgpu_silk_rate_ctl *)dctl.p, (const opusgpu_ec_state *)dec.p, 1, nullptr);
-    if (rc == OPUSGPU_OK && hipMemcpy(ctl, dctl.p, sizeof(*ctl), hipMemcpyDeviceToHost) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    if (rc == OPUSGPU_OK && ctl->status != OPUSGPU_OK) rc = ctl->status;
-    free(h_ec);
+    DevBuf dec(sizeof(opusgpu_ec_state));
+    int rc = dec.p ? bad.rc : OPUSGPU_ALLOC_FAIL;
+    if (rc == OPUSGPU_OK) rc = h2d(dec.p, h_ec.p, sizeof(opusgpu_ec_state));
+    if (rc == OPUSGPU_OK) rc = run_in_place(ctl, sizeof(*ctl), [&](void *d) {
+        return opusgpu_silk_rate_control_batch((opusgpu_silk_rate_ctl *)d, (const opusgpu_ec_state *)dec.p, 1, nullptr);
+    });
+    if (rc == OPUSGPU_OK) rc = ctl->status;
     return rc;
 }
 
@@ -121,16 +85,14 @@ void indices_to_record(opusgpu_silk_bits_in *r, const char *sCmn)
 extern "C" void opusgpu_silk_encode_indices(void *psEncC, void *psRangeEnc, int FrameIndex, int encode_LBRR, int condCoding)
 {
     (void)FrameIndex;
-    if (!psEncC || !psRangeEnc) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
-    if (encode_LBRR) { opusgpu_set_last_error(OPUSGPU_UNIMPLEMENTED); return; }
+    if (!psEncC || !psRangeEnc) { fail(OPUSGPU_BAD_ARG); return; }
+    if (encode_LBRR) { fail(OPUSGPU_UNIMPLEMENTED); return; }
     opusgpu_silk_bits_in in;
     opusgpu_silk_bits_out out;
     memset(&in, 0, sizeof(in));
     indices_to_record(&in, (const char *)psEncC);
     in.condCoding = condCoding; in.which = 1;
-    const int rc = run_bits(in, (ref_ec_ctx *)psRangeEnc, &out);
-    opusgpu_set_last_error(rc);
-    if (rc != OPUSGPU_OK) return;
+    if (fail(run_bits(in, (ref_ec_ctx *)psRangeEnc, &out)) != OPUSGPU_OK) return;
     wr_int(psEncC, OPUSGPU_REF_OFF_EC_PREV_SIGNAL_TYPE, out.ec_prevSignalType);
     wr_i16(psEncC, OPUSGPU_REF_OFF_EC_PREV_LAG_INDEX, (int16_t)out.ec_prevLagIndex);
 }
@@ -138,14 +100,14 @@ extern "C" void opusgpu_silk_encode_indices(void *psEncC, void *psRangeEnc, int 
 // silk_encode_pulses(psRangeEnc, signalType, quantOffsetType, pulses, frame_length) -- opus-fix/silk/encode_pulses.c:64-205
 extern "C" void opusgpu_silk_encode_pulses(void *psRangeEnc, int signalType, int quantOffsetType, int8_t pulses[], int frame_length)
 {
-    if (!psRangeEnc || !pulses || frame_length < 1 || frame_length > OPUSGPU_SILK_MAX_FRAME) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!psRangeEnc || !pulses || frame_length < 1 || frame_length > OPUSGPU_SILK_MAX_FRAME) { fail(OPUSGPU_BAD_ARG); return; }
     opusgpu_silk_bits_in in;
     opusgpu_silk_bits_out out;
     memset(&in, 0, sizeof(in));
     memcpy(in.pulses, pulses, (size_t)frame_length);
     in.signalType = signalType; in.quantOffsetType = quantOffsetType; in.frame_length = frame_length; in.which = 2;
     in.nb_subfr = 4; in.fs_kHz = 16; in.predictLPCOrder = 16;                      // not read by this call; values the record check accepts
-    opusgpu_set_last_error(run_bits(in, (ref_ec_ctx *)psRangeEnc, &out));
+    fail(run_bits(in, (ref_ec_ctx *)psRangeEnc, &out));
 }
 
 // silk_encode_frame_FIX(psEnc, pnBytesOut, psRangeEnc, condCoding, maxBits, useCBR) -- opus-fix/silk/fixed/encode_frame_FIX.c:88-466.
@@ -153,7 +115,7 @@ extern "C" void opusgpu_silk_encode_pulses(void *psRangeEnc, int signalType, int
 // path (a bandwidth-transition low-pass, silk_LP_variable_cutoff with sLP.mode != 0; in-band LBRR).
 extern "C" int opusgpu_silk_encode_frame_FIX(void *psEnc, int32_t *pnBytesOut, void *psRangeEnc, int condCoding, int maxBits, int useCBR)
 {
-    if (!psEnc || !pnBytesOut || !psRangeEnc) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return -1; }
+    if (!psEnc || !pnBytesOut || !psRangeEnc) { fail(OPUSGPU_BAD_ARG); return -1; }
     char *sCmn = (char *)psEnc + OPUSGPU_REF_OFF_FIX_SCMN, *ind = sCmn + OPUSGPU_REF_OFF_INDICES, *shp = (char *)psEnc + OPUSGPU_REF_OFF_FIX_SSHAPE;
     ref_ec_ctx *e = (ref_ec_ctx *)psRangeEnc;
     const int fs_kHz = rd_int(sCmn, OPUSGPU_REF_OFF_FS_KHZ), nb_subfr = rd_int(sCmn, OPUSGPU_REF_OFF_NB_SUBFR);
@@ -162,7 +124,7 @@ extern "C" int opusgpu_silk_encode_frame_FIX(void *psEnc, int32_t *pnBytesOut, v
     const int la_shape = 5 * fs_kHz;                                                // LA_SHAPE_MS * fs_kHz (silk/define.h)
     if (!((fs_kHz == 8 || fs_kHz == 12 || fs_kHz == 16) && (nb_subfr == 2 || nb_subfr == 4) && frame_length == 5 * fs_kHz * nb_subfr &&
           ltp_mem_length == 20 * fs_kHz && la_pitch >= 0 && la_pitch + frame_length + ltp_mem_length <= OPUSGPU_SILK_PITCH_BUF)) {
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
+        fail(OPUSGPU_BAD_ARG);
         return -1;
     }
     // Everything a later stage would refuse is refused HERE, before the first write to *psEnc, so that OPUSGPU_UNIMPLEMENTED
@@ -173,7 +135,7 @@ extern "C" int opusgpu_silk_encode_frame_FIX(void *psEnc, int32_t *pnBytesOut, v
     // already out with 12 kHz).
     if (rd_int(sCmn + OPUSGPU_REF_OFF_SLP, OPUSGPU_REF_OFF_LP_MODE) != 0 || (!prefill && rd_int(sCmn, OPUSGPU_REF_OFF_LBRR_ENABLED) != 0) ||
         fs_kHz == 12 || (frame_length & 15) != 0) {
-        opusgpu_set_last_error(OPUSGPU_UNIMPLEMENTED);
+        fail(OPUSGPU_UNIMPLEMENTED);
         return -1;
     }
     const int fc = rd_int(sCmn, OPUSGPU_REF_OFF_FRAME_COUNTER);                     // :128
@@ -270,8 +232,7 @@ extern "C" int opusgpu_silk_encode_frame_FIX(void *psEnc, int32_t *pnBytesOut, v
         }
         free(ctrl); free(res_pitch); free(xfw_Q3); free(nsq_copy); free(nsq_copy2); free(ec_buf_copy);
     }
-    opusgpu_set_last_error(rc);
-    if (rc != OPUSGPU_OK) return -1;
+    if (fail(rc) != OPUSGPU_OK) return -1;
     memmove(x_buf, x_buf + frame_length, sizeof(int16_t) * (size_t)(ltp_mem_length + la_shape));                                // :425
     if (prefill) { *pnBytesOut = 0; return 0; }
     wr_int(sCmn, OPUSGPU_REF_OFF_FIRST_FRAME_AFTER_RESET, 0);                      // :444

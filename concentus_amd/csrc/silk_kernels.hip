@@ -20,7 +20,7 @@
 // 16x32 products are evaluated on split halves (full-rate 24-bit multiplier), 32x32 ones as 64-bit.
 #include <string.h>
 #include "silk_burg_dev.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 #include "../../include/opusgpu_silk.h"
 #include "silk_validate.h"
 
@@ -674,26 +674,18 @@ extern "C" void opusgpu_silk_burg_modified_c(int32_t *res_nrg, int *res_nrg_Q, i
     (void)arch;
     if (!res_nrg || !res_nrg_Q || !A_Q16 || !x || D < 1 || D > OPUSGPU_SILK_MAX_ORDER || nb_subfr < 1 || subfr_length <= D ||
         subfr_length * nb_subfr > OPUSGPU_SILK_BURG_MAX_X) {
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
+        fail(OPUSGPU_BAD_ARG);
         return;
     }
     opusgpu_burg_in h_in;
+    opusgpu_burg_out h_out;
     memset(&h_in, 0, sizeof(h_in));
     memcpy(h_in.x, x, sizeof(int16_t) * (size_t)subfr_length * nb_subfr);
     h_in.minInvGain_Q30 = minInvGain_Q30; h_in.subfr_length = subfr_length; h_in.nb_subfr = nb_subfr; h_in.D = D;
-    opusgpu_burg_in *d_in = nullptr;
-    opusgpu_burg_out *d_out = nullptr, h_out;
-    if (hipMalloc(&d_in, sizeof(h_in)) != hipSuccess || hipMalloc(&d_out, sizeof(h_out)) != hipSuccess) {
-        opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL);
-        if (d_in) (void)hipFree(d_in);
-        return;
-    }
-    int rc = opusgpu_copy(d_in, &h_in, sizeof(h_in), hipMemcpyHostToDevice);
-    if (rc == OPUSGPU_OK) rc = opusgpu_silk_burg_modified_batch(d_in, d_out, 1, nullptr);
-    if (rc == OPUSGPU_OK && hipMemcpy(&h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    opusgpu_set_last_error(rc);
+    // Unchecked: the arguments were checked above and the out record has no status word
+    const int rc = fail(run_record<Unchecked>(&h_in, &h_out, (NoState *)nullptr, [](const opusgpu_burg_in *i, NoState *, opusgpu_burg_out *o) {
+        return opusgpu_silk_burg_modified_batch(i, o, 1, nullptr);
+    }));
     if (rc != OPUSGPU_OK) return;
     *res_nrg = h_out.res_nrg;
     *res_nrg_Q = h_out.res_nrg_Q;

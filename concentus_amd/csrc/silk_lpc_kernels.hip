@@ -6,7 +6,7 @@
 // use is a conflict-free ds_read instead of a 2-byte load at an 832-byte stride between lanes.
 #include <string.h>
 #include "silk_lpc_dev.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 #include "../../include/opusgpu_silk.h"
 #include "../../include/opusgpu_hooks.h"
 #include "silk_validate.h"
@@ -76,12 +76,11 @@ extern "C" int opusgpu_silk_find_lpc_batch(const opusgpu_find_lpc_in *d_in, opus
 // Per-call hook with the reference's own argument list: silk_find_LPC_FIX(psEncC, NLSF_Q15, x, minInvGain_Q30)
 // (silk/fixed/main_FIX.h; called at silk/fixed/find_pred_coefs_FIX.c:136). psEncC is the reference's silk_encoder_state
 // (x86-64 layout): the fields read and the one written are reached at the offsets of include/opusgpu_hooks.h.
-static int rd_int(const void *base, int off) { int v; memcpy(&v, (const char *)base + off, sizeof(v)); return v; }
-
 extern "C" void opusgpu_silk_find_LPC_FIX(void *psEncC, int16_t NLSF_Q15[], const int16_t x[], const int32_t minInvGain_Q30)
 {
-    if (!psEncC || !NLSF_Q15 || !x) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!psEncC || !NLSF_Q15 || !x) { fail(OPUSGPU_BAD_ARG); return; }
     opusgpu_find_lpc_in h_in;
+    opusgpu_find_lpc_out h_out;
     memset(&h_in, 0, sizeof(h_in));
     h_in.minInvGain_Q30 = minInvGain_Q30;
     h_in.subfr_length = rd_int(psEncC, OPUSGPU_REF_OFF_SUBFR_LENGTH);
@@ -92,26 +91,13 @@ extern "C" void opusgpu_silk_find_LPC_FIX(void *psEncC, int16_t NLSF_Q15[], cons
     memcpy(h_in.prev_NLSFq_Q15, (const char *)psEncC + OPUSGPU_REF_OFF_PREV_NLSFQ_Q15, sizeof(h_in.prev_NLSFq_Q15));
     const long nx = (long)(h_in.subfr_length + h_in.predictLPCOrder) * h_in.nb_subfr;
     if (h_in.nb_subfr < 1 || h_in.subfr_length < 1 || h_in.predictLPCOrder < 1 || nx > OPUSGPU_SILK_BURG_MAX_X) {
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
+        fail(OPUSGPU_BAD_ARG);
         return;
     }
     memcpy(h_in.x, x, sizeof(int16_t) * (size_t)nx);
-    opusgpu_find_lpc_in *d_in = nullptr;
-    opusgpu_find_lpc_out *d_out = nullptr, h_out;
-    if (hipMalloc(&d_in, sizeof(h_in)) != hipSuccess || hipMalloc(&d_out, sizeof(h_out)) != hipSuccess) {
-        opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL);
-        if (d_in) (void)hipFree(d_in);
-        return;
-    }
-    int rc = hipMemcpy(d_in, &h_in, sizeof(h_in), hipMemcpyHostToDevice) == hipSuccess ? OPUSGPU_OK : OPUSGPU_INTERNAL_ERROR;
-    OpusgpuHookBadScope bad;                 // rejected records count into this thread's counter, not the device's shared one
-    if (rc == OPUSGPU_OK) rc = bad.rc;
-    if (rc == OPUSGPU_OK) rc = opusgpu_silk_find_lpc_batch(d_in, d_out, 1, nullptr);
-    if (rc == OPUSGPU_OK && hipMemcpy(&h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (rc == OPUSGPU_OK && h_out.status != OPUSGPU_OK) rc = h_out.status;
-    opusgpu_set_last_error(rc);
+    const int rc = fail(run_record(&h_in, &h_out, (NoState *)nullptr, [](const opusgpu_find_lpc_in *i, NoState *, opusgpu_find_lpc_out *o) {
+        return opusgpu_silk_find_lpc_batch(i, o, 1, nullptr);
+    }));
     if (rc != OPUSGPU_OK) return;
     memcpy(NLSF_Q15, h_out.NLSF_Q15, sizeof(int16_t) * (size_t)h_in.predictLPCOrder);
     *((int8_t *)psEncC + OPUSGPU_REF_OFF_INDICES + OPUSGPU_REF_OFF_NLSF_INTERP_COEF_Q2) = (int8_t)h_out.NLSFInterpCoef_Q2;

@@ -3,7 +3,7 @@
 // (find_pred_coefs_FIX.c:139-143). One lane per record; the arithmetic lives in silk_nlsf_dev.h.
 #include <string.h>
 #include "silk_nlsf_dev.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 #include "../../include/opusgpu_silk.h"
 #include "../../include/opusgpu_hooks.h"
 #include "silk_validate.h"
@@ -112,32 +112,10 @@ extern "C" int opusgpu_silk_residual_energy_batch(const opusgpu_res_nrg_in *d_in
 }
 
 // ---- per-call hooks with the reference's own argument lists ------------------------------------------------------------
-static int rd_int(const void *base, int off) { int v; memcpy(&v, (const char *)base + off, sizeof(v)); return v; }
-
-template <class In, class Out, class Launch>
-static int run_one(const In &h_in, Out &h_out, Launch launch)
-{
-    In *d_in = nullptr;
-    Out *d_out = nullptr;
-    if (hipMalloc(&d_in, sizeof(In)) != hipSuccess || hipMalloc(&d_out, sizeof(Out)) != hipSuccess) {
-        if (d_in) (void)hipFree(d_in);
-        return OPUSGPU_ALLOC_FAIL;
-    }
-    int rc = hipMemcpy(d_in, &h_in, sizeof(In), hipMemcpyHostToDevice) == hipSuccess ? OPUSGPU_OK : OPUSGPU_INTERNAL_ERROR;
-    OpusgpuHookBadScope bad;                 // rejected records count into this thread's counter, not the device's shared one
-    if (rc == OPUSGPU_OK) rc = bad.rc;
-    if (rc == OPUSGPU_OK) rc = launch(d_in, d_out);
-    if (rc == OPUSGPU_OK && hipMemcpy(&h_out, d_out, sizeof(Out), hipMemcpyDeviceToHost) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (rc == OPUSGPU_OK && h_out.status != OPUSGPU_OK) rc = h_out.status;
-    return rc;
-}
-
 // silk_process_NLSFs(psEncC, PredCoef_Q12, pNLSF_Q15, prev_NLSFq_Q15) (silk/main.h; called at silk/fixed/find_pred_coefs_FIX.c:139)
 extern "C" void opusgpu_silk_process_NLSFs(void *psEncC, int16_t PredCoef_Q12[/*2 * 16*/], int16_t pNLSF_Q15[], const int16_t prev_NLSFq_Q15[])
 {
-    if (!psEncC || !PredCoef_Q12 || !pNLSF_Q15 || !prev_NLSFq_Q15) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!psEncC || !PredCoef_Q12 || !pNLSF_Q15 || !prev_NLSFq_Q15) { fail(OPUSGPU_BAD_ARG); return; }
     opusgpu_process_nlsf_in h_in;
     opusgpu_process_nlsf_out h_out;
     memset(&h_in, 0, sizeof(h_in));
@@ -150,13 +128,12 @@ extern "C" void opusgpu_silk_process_NLSFs(void *psEncC, int16_t PredCoef_Q12[/*
     h_in.NLSFInterpCoef_Q2 = indices[OPUSGPU_REF_OFF_NLSF_INTERP_COEF_Q2];
     h_in.signalType = indices[OPUSGPU_REF_OFF_SIGNAL_TYPE];
     const int D = h_in.predictLPCOrder;
-    if (D != 10 && D != 16) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (D != 10 && D != 16) { fail(OPUSGPU_BAD_ARG); return; }
     memcpy(h_in.NLSF_Q15, pNLSF_Q15, sizeof(int16_t) * (size_t)D);
     memcpy(h_in.prev_NLSFq_Q15, prev_NLSFq_Q15, sizeof(int16_t) * (size_t)D);
-    const int rc = run_one(h_in, h_out, [](const opusgpu_process_nlsf_in *i, opusgpu_process_nlsf_out *o) {
+    const int rc = fail(run_record(&h_in, &h_out, (NoState *)nullptr, [](const opusgpu_process_nlsf_in *i, NoState *, opusgpu_process_nlsf_out *o) {
         return opusgpu_silk_process_nlsfs_batch(i, o, 1, nullptr);
-    });
-    opusgpu_set_last_error(rc);
+    }));
     if (rc != OPUSGPU_OK) return;
     memcpy(PredCoef_Q12, h_out.PredCoef_Q12[0], sizeof(int16_t) * (size_t)D);
     memcpy(PredCoef_Q12 + OPUSGPU_SILK_MAX_ORDER, h_out.PredCoef_Q12[1], sizeof(int16_t) * (size_t)D);
@@ -170,10 +147,10 @@ extern "C" void opusgpu_silk_residual_energy_FIX(int32_t nrgs[], int nrgsQ[], co
                                                  const int subfr_length, const int nb_subfr, const int LPC_order, int arch)
 {
     (void)arch;
-    if (!nrgs || !nrgsQ || !x || !a_Q12 || !gains) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
+    if (!nrgs || !nrgsQ || !x || !a_Q12 || !gains) { fail(OPUSGPU_BAD_ARG); return; }
     const long nx = (long)(subfr_length + LPC_order) * nb_subfr;
     if ((nb_subfr != 2 && nb_subfr != 4) || subfr_length < 1 || LPC_order < 2 || LPC_order > 16 || nx > OPUSGPU_SILK_BURG_MAX_X) {
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
+        fail(OPUSGPU_BAD_ARG);
         return;
     }
     opusgpu_res_nrg_in h_in;
@@ -184,10 +161,9 @@ extern "C" void opusgpu_silk_residual_energy_FIX(int32_t nrgs[], int nrgsQ[], co
     memcpy(h_in.a_Q12[1], a_Q12 + OPUSGPU_SILK_MAX_ORDER, sizeof(int16_t) * (size_t)LPC_order);
     memcpy(h_in.gains, gains, sizeof(int32_t) * (size_t)nb_subfr);
     h_in.subfr_length = subfr_length; h_in.nb_subfr = nb_subfr; h_in.LPC_order = LPC_order;
-    const int rc = run_one(h_in, h_out, [](const opusgpu_res_nrg_in *i, opusgpu_res_nrg_out *o) {
+    const int rc = fail(run_record(&h_in, &h_out, (NoState *)nullptr, [](const opusgpu_res_nrg_in *i, NoState *, opusgpu_res_nrg_out *o) {
         return opusgpu_silk_residual_energy_batch(i, o, 1, nullptr);
-    });
-    opusgpu_set_last_error(rc);
+    }));
     if (rc != OPUSGPU_OK) return;
     for (int k = 0; k < nb_subfr; k++) { nrgs[k] = h_out.nrgs[k]; nrgsQ[k] = h_out.nrgsQ[k]; }
 }

@@ -6,7 +6,7 @@
 #include <string.h>
 #include "silk_pred_dev.h"
 #include "silk_gains_dev.h"
-#include "opusgpu_internal.h"
+#include "hook_host.h"
 #include "../../include/opusgpu_silk.h"
 #include "../../include/opusgpu_hooks.h"
 #include "silk_validate.h"
@@ -118,17 +118,12 @@ extern "C" int opusgpu_silk_find_pred_coefs_batch(const opusgpu_find_pred_coefs_
 // silk_encoder_control_FIX (x86-64 layout): the fields read and written are reached at the offsets of include/opusgpu_hooks.h.
 // x must be preceded by ltp_mem_length samples (it points into psEnc->x_buf, encode_frame_FIX.c), res_pitch holds
 // ltp_mem_length + frame_length samples.
-static int rd_int(const void *base, int off) { int v; memcpy(&v, (const char *)base + off, sizeof(v)); return v; }
-static void wr_int(void *base, int off, int v) { memcpy((char *)base + off, &v, sizeof(v)); }
-
 extern "C" void opusgpu_silk_find_pred_coefs_FIX(void *psEnc, void *psEncCtrl, const int16_t res_pitch[], const int16_t x[], int condCoding)
 {
-    if (!psEnc || !psEncCtrl || !res_pitch || !x) { opusgpu_set_last_error(OPUSGPU_BAD_ARG); return; }
-    static opusgpu_find_pred_coefs_in h_in_zero;
-    opusgpu_find_pred_coefs_in *h_in = (opusgpu_find_pred_coefs_in *)malloc(sizeof(*h_in));
+    if (!psEnc || !psEncCtrl || !res_pitch || !x) { fail(OPUSGPU_BAD_ARG); return; }
+    HeapRec<opusgpu_find_pred_coefs_in> h_in;
     opusgpu_find_pred_coefs_out h_out;
-    if (!h_in) { opusgpu_set_last_error(OPUSGPU_ALLOC_FAIL); return; }
-    *h_in = h_in_zero;
+    if (!h_in.p) { fail(OPUSGPU_ALLOC_FAIL); return; }
     char *sCmn = (char *)psEnc + OPUSGPU_REF_OFF_FIX_SCMN;
     char *ind = sCmn + OPUSGPU_REF_OFF_INDICES;
     h_in->nb_subfr = rd_int(sCmn, OPUSGPU_REF_OFF_NB_SUBFR);
@@ -152,28 +147,16 @@ extern "C" void opusgpu_silk_find_pred_coefs_FIX(void *psEnc, void *psEncCtrl, c
     memcpy(h_in->prev_NLSFq_Q15, sCmn + OPUSGPU_REF_OFF_PREV_NLSFQ_Q15, sizeof(h_in->prev_NLSFq_Q15));
     const int nb = h_in->nb_subfr, L = h_in->subfr_length, D = h_in->predictLPCOrder, ltp = h_in->ltp_mem_length;
     if ((nb != 2 && nb != 4) || L < 1 || L > 80 || (D != 10 && D != 16) || ltp < D || ltp > OPUSGPU_SILK_MAX_LTP_MEM) {
-        free(h_in);
-        opusgpu_set_last_error(OPUSGPU_BAD_ARG);
+        fail(OPUSGPU_BAD_ARG);
         return;
     }
     memcpy(h_in->res_pitch, res_pitch, sizeof(int16_t) * (size_t)(ltp + nb * L));
     memcpy(h_in->x, x - ltp, sizeof(int16_t) * (size_t)(ltp + nb * L));
-    opusgpu_find_pred_coefs_in *d_in = nullptr;
-    opusgpu_find_pred_coefs_out *d_out = nullptr;
-    int rc = OPUSGPU_OK;
-    if (hipMalloc(&d_in, sizeof(*h_in)) != hipSuccess || hipMalloc(&d_out, sizeof(h_out)) != hipSuccess) rc = OPUSGPU_ALLOC_FAIL;
-    if (rc == OPUSGPU_OK && hipMemcpy(d_in, h_in, sizeof(*h_in), hipMemcpyHostToDevice) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    OpusgpuHookBadScope bad;                 // rejected records count into this thread's counter, not the device's shared one
-    if (rc == OPUSGPU_OK) rc = bad.rc;
-    if (rc == OPUSGPU_OK) rc = opusgpu_silk_find_pred_coefs_batch(d_in, d_out, 1, nullptr);
-    if (rc == OPUSGPU_OK && hipMemcpy(&h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost) != hipSuccess) rc = OPUSGPU_INTERNAL_ERROR;
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    const int voiced = h_in->signalType == 2;
-    free(h_in);
-    if (rc == OPUSGPU_OK && h_out.status != OPUSGPU_OK) rc = h_out.status;
-    opusgpu_set_last_error(rc);
+    const int rc = fail(run_record(h_in.p, &h_out, (NoState *)nullptr, [](const opusgpu_find_pred_coefs_in *i, NoState *, opusgpu_find_pred_coefs_out *o) {
+        return opusgpu_silk_find_pred_coefs_batch(i, o, 1, nullptr);
+    }));
     if (rc != OPUSGPU_OK) return;
+    const int voiced = h_in->signalType == 2;
     char *ctl = (char *)psEncCtrl;
     memcpy(ctl + OPUSGPU_REF_OFF_CTRL_PRED_COEF_Q12, h_out.PredCoef_Q12[0], sizeof(int16_t) * (size_t)D);
     memcpy(ctl + OPUSGPU_REF_OFF_CTRL_PRED_COEF_Q12 + 2 * OPUSGPU_SILK_MAX_ORDER, h_out.PredCoef_Q12[1], sizeof(int16_t) * (size_t)D);
