@@ -13,6 +13,7 @@
 // Data-parallel loops are strided over the lanes; scalar decisions run identically on every lane and
 // only lane 0 stores ("st0"). The arithmetic of every element follows the reference bit for bit.
 #pragma once
+#include <stddef.h>
 #include "celt_math.h"
 #include "celt_state.h"
 #include "device_tables.h"
@@ -341,14 +342,29 @@ CA_DEVFN void pitch_downsample_wave(L &F, const FrameCtx &fc)              // pi
     // ac[k] = sum_{i=0}^{n-1-k} xs[i]*xs[i+k] with xs = PSHR32(x_lp, sh): the reference's fastN split
     // (celt_pitch_xcorr over fastN + tail loop) adds up to exactly this, and MAC16_16 sums wrap.
     (void)fastN;
-    for (int k = 0; k <= lag; k++) {
-        i32 p = 0;
-        for (int i = (h0 ? h0 - LANES : 0) + lane(); i + k < n; i += LANES) {       // products with x_lp[i < h0] are zero
-            i32 a = sh ? (i16)pshr32(x_lp[i], sh) : x_lp[i];
-            i32 b = sh ? (i16)pshr32(x_lp[i + k], sh) : x_lp[i + k];
-            p = mac16_16(p, a, b);
+    {   // All five lags in one pass, two samples per lane per trip: the words (xs[2p], xs[2p+1]), (xs[2p+2], xs[2p+3]),
+        // (xs[2p+4], xs[2p+5]) hold every partner of the pair at 2p. Words past the end count as zeros, which is the
+        // i + k < n bound of every lag; the pairs below h0 are zeros themselves (cleared above) and are skipped.
+        static_assert(alignof(L) % 4 == 0 && offsetof(L, s.pitch.buf) % 4 == 0 && ((MAXP + FRAME) >> 1) % 2 == 0 && (MAXP >> 1) % 2 == 0,
+                      "x_lp is read as 32-bit words of two samples");
+        const u32a *xw = reinterpret_cast<const u32a *>(x_lp);
+        const int nw = n >> 1;
+        if (sh) CA_COUNT("pitch.autocorr_shifted", sh);
+        i32 p0 = 0, p1 = 0, p2 = 0, p3 = 0, p4 = 0;
+        for (int p = (h0 >> 1) + lane(); p < nw; p += LANES) {
+            u32 w0 = xw[p], w1 = p + 1 < nw ? xw[p + 1] : 0u, w2 = p + 2 < nw ? xw[p + 2] : 0u;
+            if (sh) {                                                              // xs = PSHR32(x_lp, sh), sample by sample
+                w0 = pack_i16(pshr32((i16)w0, sh), pshr32((i32)w0 >> 16, sh));
+                w1 = pack_i16(pshr32((i16)w1, sh), pshr32((i32)w1 >> 16, sh));
+                w2 = pack_i16(pshr32((i16)w2, sh), pshr32((i32)w2 >> 16, sh));
+            }
+            p0 = dot2_i16(w0, w0, p0);
+            p1 = dot2_i16(w0, pair_next(w0, w1), p1);
+            p2 = dot2_i16(w0, w1, p2);
+            p3 = dot2_i16(w0, pair_next(w1, w2), p3);
+            p4 = dot2_i16(w0, w2, p4);
         }
-        ac[k] = wave_add(p);
+        ac[0] = wave_add(p0); ac[1] = wave_add(p1); ac[2] = wave_add(p2); ac[3] = wave_add(p3); ac[4] = wave_add(p4);
     }
     int shift2x = 2 * sh;
     if (shift2x <= 0) ac[0] = add32(ac[0], shl32(1, -shift2x));
@@ -545,7 +561,7 @@ CA_DEVFN int pitch_search_wave(L &F, bool zero_hist)
     // coarse search, 4x decimation: celt_pitch_xcorr(x4, y4, xcorr, 240, 244). Each lane owns four consecutive lags
     // and slides an 8-sample window of y4 along x4 (the shape of xcorr_kernel, pitch.h:61-129): per four samples one
     // 8-byte read of x4 (a broadcast) and one of y4 instead of eight 2-byte reads, and a 60-trip loop instead of 4 x 240.
-    // The sums wrap (MAC16_16), so the order of accumulation is free.
+    // The sums wrap (MAC16_16), so the order of accumulation is free: the products go in two at a time (dot2_i16).
     static_assert(((MAXP - 3 * MINP) >> 2) % 4 == 0 && (FRAME >> 2) % 4 == 0, "244 lags = 61 groups of 4; 240 samples = 60 groups of 4");
     i32 mc = 1;
     for (int i0 = 4 * lane(); i0 < (max_pitch >> 2); i0 += 4 * LANES) {
@@ -556,14 +572,16 @@ CA_DEVFN int pitch_search_wave(L &F, bool zero_hist)
 #pragma unroll 4
 #endif
         for (int c = 0; c < (len >> 4); c++) {
+            // the words already hold the sample pairs (x0,x1) (x2,x3) and (y0,y1) (y2,y3) (y4,y5) (y6,.): only the pairs
+            // at odd offsets have to be built, and nothing is unpacked
             const int2 w1 = yv[c + 1], xx = xv[c];
-            const i32 x0 = (i16)xx.x, x1 = xx.x >> 16, x2 = (i16)xx.y, x3 = xx.y >> 16;
-            const i32 y0 = (i16)w0.x, y1 = w0.x >> 16, y2 = (i16)w0.y, y3 = w0.y >> 16;
-            const i32 y4_ = (i16)w1.x, y5 = w1.x >> 16, y6 = (i16)w1.y;
-            s0 = add32(s0, add32(add32(__mul24(x0, y0), __mul24(x1, y1)), add32(__mul24(x2, y2), __mul24(x3, y3))));
-            s1 = add32(s1, add32(add32(__mul24(x0, y1), __mul24(x1, y2)), add32(__mul24(x2, y3), __mul24(x3, y4_))));
-            s2 = add32(s2, add32(add32(__mul24(x0, y2), __mul24(x1, y3)), add32(__mul24(x2, y4_), __mul24(x3, y5))));
-            s3 = add32(s3, add32(add32(__mul24(x0, y3), __mul24(x1, y4_)), add32(__mul24(x2, y5), __mul24(x3, y6))));
+            const u32 xa = (u32)xx.x, xb = (u32)xx.y;
+            const u32 y01 = (u32)w0.x, y23 = (u32)w0.y, y45 = (u32)w1.x;
+            const u32 y12 = pair_next(y01, y23), y34 = pair_next(y23, y45), y56 = pair_next(y45, (u32)w1.y);
+            s0 = dot2_i16(xb, y23, dot2_i16(xa, y01, s0));
+            s1 = dot2_i16(xb, y34, dot2_i16(xa, y12, s1));
+            s2 = dot2_i16(xb, y45, dot2_i16(xa, y23, s2));
+            s3 = dot2_i16(xb, y56, dot2_i16(xa, y34, s3));
             w0 = w1;
         }
         xcorr[i0] = s0; xcorr[i0 + 1] = s1; xcorr[i0 + 2] = s2; xcorr[i0 + 3] = s3;
@@ -604,13 +622,30 @@ CA_DEVFN int pitch_search_wave(L &F, bool zero_hist)
     return 2 * best_pitch[0] - offset;
 }
 
-// inner products over the half-rate pitch buffer: sum_{i<N} x[i]*y1[i], x[i]*y2[i]  (pitch.h:132-160)
-CA_DEV void dual_inner_prod_wave(const i16 *x, const i16 *y1, const i16 *y2, int N, i32 &xy1, i32 &xy2)
+// Inner products of the half-rate pitch buffer with itself T samples earlier, sum_{i<N} x[i]*x[i-T]  (celt_inner_prod /
+// dual_inner_prod, pitch.h:132-175), two samples per lane per trip. x is 4-byte aligned and N even, so x[2p], x[2p+1] are
+// one word; x[2p-T], x[2p+1-T] are one word for an even T and straddle two for an odd one (T is wave-uniform). LagView
+// holds the aligned word pointer at or below x - T and the parity; both words are read either way, the parity only
+// sets the v_alignbit shift. The highest sample a view touches is x[N+1-T], so T >= 2 keeps the reads inside x[0..N).
+struct LagView { const u32a *w; int odd; };
+CA_DEV LagView lag_view(const i16 *x, int T)
 {
-    i32 a = 0, b = 0;
-    for (int i = lane(); i < N; i += LANES) { a = mac16_16(a, x[i], y1[i]); b = mac16_16(b, x[i], y2[i]); }
-    xy1 = wave_add(a);
-    xy2 = wave_add(b);
+    LagView v;
+    v.odd = T & 1;
+    v.w = reinterpret_cast<const u32a *>(x - T - v.odd);
+    CA_COUNT(v.odd ? "pitch.lag_odd" : "pitch.lag_even", T);
+    return v;
+}
+CA_DEV u32 lag_pair(const LagView &v, int p) { return pair_at(v.w[p], v.w[p + 1], v.odd); }
+
+// one lane's share of sum_{i<N} x[i]*x[i-T]
+CA_DEV i32 lag_prod_part(const i16 *x, int T, int N)
+{
+    const u32a *xw = reinterpret_cast<const u32a *>(x);
+    const LagView v = lag_view(x, T);
+    i32 s = 0;
+    for (int p = lane(); p < (N >> 1); p += LANES) s = dot2_i16(xw[p], lag_pair(v, p), s);
+    return s;
 }
 
 CA_DEV i32 pitch_gain_from(i32 xy, i32 xx, i32 yy, bool halve)                      // pitch.c:406-421,:455-460
@@ -634,8 +669,17 @@ CA_DEVFN i32 remove_doubling_wave(L &F, int *T0_, int prev_period, i32 prev_gain
     if (*T0_ >= maxperiod) *T0_ = maxperiod - 1;
     int T, T0;
     T = T0 = *T0_;
+    static_assert((MAXP / 2) % 2 == 0 && (FRAME / 2) % 2 == 0 && alignof(L) % 4 == 0 && offsetof(L, s.pitch.buf) % 4 == 0,
+                  "x = buf + 512 is read as 32-bit words of two samples");
     i32 xx, xy;
-    dual_inner_prod_wave(x, x, x - T0, N, xx, xy);
+    {
+        const u32a *xw = reinterpret_cast<const u32a *>(x);
+        const LagView v = lag_view(x, T0);
+        i32 a = 0, b = 0;
+        for (int p = lane(); p < (N >> 1); p += LANES) { const u32 xv = xw[p]; a = dot2_i16(xv, xv, a); b = dot2_i16(xv, lag_pair(v, p), b); }
+        xx = wave_add(a);
+        xy = wave_add(b);
+    }
     {   // yy_lookup[i] = max(0, xx + sum_{j=1..i} (x[-j]^2 - x[N-j]^2)): a prefix sum (wrap-around adds commute),
         // scanned LANES entries at a time
         st0(&yy_lookup[0], xx);
@@ -659,9 +703,17 @@ CA_DEVFN i32 remove_doubling_wave(L &F, int *T0_, int prev_period, i32 prev_gain
         if (T1 < minperiod) break;
         if (k == 2) T1b = (T1 + T0 > maxperiod) ? T0 : T0 + T1;
         else T1b = (2 * CLT_second_check[k] * T0 + k) / (2 * k);
-        i32 xy2;
-        dual_inner_prod_wave(x, x - T1, x - T1b, N, xy, xy2);
-        xy = add32(xy, xy2);
+        // only xy(T1) + xy(T1b) is used (pitch.c:437-440) and the sums wrap: one accumulator, one reduction
+        {
+            const u32a *xw = reinterpret_cast<const u32a *>(x);
+            const LagView v1 = lag_view(x, T1), v2 = lag_view(x, T1b);
+            i32 a = 0;
+            for (int p = lane(); p < (N >> 1); p += LANES) {
+                const u32 xv = xw[p];
+                a = dot2_i16(xv, lag_pair(v2, p), dot2_i16(xv, lag_pair(v1, p), a));
+            }
+            xy = wave_add(a);
+        }
         yy = add32(yy_lookup[T1], yy_lookup[T1b]);
         i32 g1 = pitch_gain_from(xy, xx, yy, false);
         int dT = T1 - prev_period;
@@ -681,10 +733,7 @@ CA_DEVFN i32 remove_doubling_wave(L &F, int *T0_, int prev_period, i32 prev_gain
     else pg = (i16)(frac_div32(best_xy, add32(best_yy, 1)) >> 16);
     i32 xc[3];
     for (int k = 0; k < 3; k++) {
-        i32 p = 0;
-        const i16 *yk = x - (T + k - 1);
-        for (int i = lane(); i < N; i += LANES) p = mac16_16(p, x[i], yk[i]);
-        xc[k] = wave_add(p);
+        xc[k] = wave_add(lag_prod_part(x, T + k - 1, N));
     }
     int offset = 0;
     if (sub32(xc[2], xc[0]) > mul16_32_q15(22938, sub32(xc[1], xc[0]))) offset = 1;

@@ -64,6 +64,34 @@ CA_DEV i32 mul16_16_q11(i32 a, i32 b) { return mul16_16(a, b) >> 11; }
 CA_DEV i32 mul16_16_p13(i32 a, i32 b) { return (4096 + mul16_16(a, b)) >> 13; }
 CA_DEV i32 mul16_16_p14(i32 a, i32 b) { return (8192 + mul16_16(a, b)) >> 14; }
 
+// ---- packed pairs of 16-bit samples ---------------------------------------------------------------------------------------
+// A 32-bit word of an i16 array holds two consecutive samples (little endian: the earlier one in the low half). Sums of
+// MAC16_16 products wrap mod 2^32 in the reference, so two products can be added before they join the accumulator:
+// v_dot2c_i32_i16 (the non-clamping form) does c + lo*lo + hi*hi in one instruction, wrapping like the C below -- also
+// when the pair sum alone overflows ((-32768)^2 * 2 = 2^31).
+typedef u32 __attribute__((may_alias)) u32a;           // a 32-bit view of an i16 array
+CA_DEV i32 dot2_i16(u32 a, u32 b, i32 c)
+{
+#if defined(CA_HOST_EMU)
+    const u32 lo = (u32)((i32)(i16)a * (i32)(i16)b), hi = (u32)((i32)(i16)(a >> 16) * (i32)(i16)(b >> 16));
+    return (i32)((u32)c + lo + hi);
+#else
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b), c, false);
+#endif
+}
+// the pair that starts `odd` (0 or 1) samples into the four samples of (w0, w1), w0 the earlier word (v_alignbit_b32)
+CA_DEV u32 pair_at(u32 w0, u32 w1, int odd)
+{
+#if defined(CA_HOST_EMU)
+    return (u32)(((u64)w1 << 32 | w0) >> (16 * odd));
+#else
+    return __builtin_amdgcn_alignbit(w1, w0, (u32)(16 * odd));
+#endif
+}
+CA_DEV u32 pair_next(u32 w0, u32 w1) { return pair_at(w0, w1, 1); }    // the pair starting one sample later
+CA_DEV u32 pack_i16(i32 lo, i32 hi) { return ((u32)lo & 0xffffu) | ((u32)hi << 16); }
+
 CA_DEV i32 shl32(i32 a, int s) { return (i32)((u32)a << s); }
 CA_DEV i32 pshr32(i32 a, int s) { return (i32)((u32)a + (u32)((1 << s) >> 1)) >> s; }
 CA_DEV i32 vshr32(i32 a, int s) { return s > 0 ? a >> s : shl32(a, -s); }

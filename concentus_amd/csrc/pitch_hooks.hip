@@ -16,15 +16,21 @@ enum { XCORR_MAX_LEN = 2048 };
 __global__ __launch_bounds__(256) void pitch_xcorr_kernel(const i16 *__restrict__ x, const i16 *__restrict__ y,
                                                           i32 *__restrict__ xcorr, int len, int max_pitch, i32 *maxcorr)
 {
-    __shared__ i16 xs[XCORR_MAX_LEN];
+    // the sums go through dot2_i16, two products at a time (the primitive of the front kernel's pitch loops, driven here at
+    // the caller's values): x staged as pairs, an odd len padded with a zero sample; y packed from its two halves, since
+    // y + i is only 2-byte aligned
+    __shared__ __attribute__((aligned(4))) i16 xs[XCORR_MAX_LEN];
     for (int j = threadIdx.x; j < len; j += blockDim.x) xs[j] = x[j];
+    if ((len & 1) && threadIdx.x == 0) xs[len] = 0;                                  // len odd => len < XCORR_MAX_LEN
     __syncthreads();
+    const u32a *xw = reinterpret_cast<const u32a *>(xs);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     i32 sum = (i32)0x80000000;
     if (i < max_pitch) {
-        u32 acc = 0;
-        for (int j = 0; j < len; j++) acc += (u32)__mul24((i32)xs[j], (i32)y[i + j]);
-        sum = (i32)acc;
+        i32 acc = 0;
+        for (int j = 0; j + 1 < len; j += 2) acc = dot2_i16(xw[j >> 1], pack_i16(y[i + j], y[i + j + 1]), acc);
+        if (len & 1) acc = dot2_i16(xw[len >> 1], pack_i16(y[i + len - 1], 0), acc);
+        sum = acc;
         xcorr[i] = sum;
     }
     const i32 m = wave_max(sum);
