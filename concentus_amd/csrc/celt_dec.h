@@ -1,7 +1,8 @@
 // celt_dec.h -- one Opus CELT-only packet -> 960 stereo samples, by ONE LANE (or the host emulation).
 //
-// Restates celt_decode_with_ec (opus-fix/celt/celt_decoder.c:713-1060) and what it calls for 48 kHz, 20 ms,
-// stereo, fullband, start 0 / end 21: the range decoder (rangedec.h), unquant_coarse/fine_energy and
+// Restates celt_decode_with_ec (opus-fix/celt/celt_decoder.c:713-1075) and what it calls for 48 kHz, 20 ms, a stereo
+// decoder (CC = 2), start 0; the packet's channel count C (1, 2) and end band (13, 17, 19, 21: NB / WB / SWB / FB) come from
+// its TOC and are run-time values of the lane: the range decoder (rangedec.h), unquant_coarse/fine_energy and
 // unquant_energy_finalise (quant_bands.c:434-539), tf_decode (celt_decoder.c:352-392), the dynalloc /
 // trim / allocation side information (compute_allocation shared with the encoder), quant_all_bands with
 // encode = 0 (bands.c:1337-1502: folding, noise fill, collapse masks, stereo merge), alg_unquant /
@@ -52,7 +53,7 @@ struct __attribute__((aligned(16))) SynthLds {
 CA_DEV u32 celt_lcg_rand(u32 seed) { return 1664525u * seed + 1013904223u; }                   // bands.c:63
 
 // ---- energies ----------------------------------------------------------------------------------------
-CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C)               // quant_bands.c:434
+CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C, int end)      // quant_bands.c:434
 {
     const u8 *prob_model = CLT_e_prob_model + (LM3 * 2 + intra) * 42;
     i32 prev[2] = {0, 0};
@@ -60,7 +61,7 @@ CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C
     if (intra) { coef = 0; beta = 4915; }                                                      // beta_intra
     else { beta = CLT_beta_coef[LM3]; coef = CLT_pred_coef[LM3]; }
     const i32 budget = (i32)dec.storage * 8;
-    for (int i = 0; i < NB; i++) {
+    for (int i = 0; i < end; i++) {
         for (int c = 0; c < C; c++) {
             int qi;
             i32 tell = ec_tell(dec);
@@ -85,9 +86,9 @@ CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C
     }
 }
 
-CA_DEV void unquant_fine_energy_dec(i16 *oldE, const i32 *fine_quant, RangeDec &dec, int C)     // quant_bands.c:490
+CA_DEV void unquant_fine_energy_dec(i16 *oldE, const i32 *fine_quant, RangeDec &dec, int C, int end)   // quant_bands.c:490
 {
-    for (int i = 0; i < NB; i++) {
+    for (int i = 0; i < end; i++) {
         if (fine_quant[i] <= 0) continue;
         for (int c = 0; c < C; c++) {
             i32 q2 = (i32)ec_dec_bits(dec, (u32)fine_quant[i]);
@@ -98,10 +99,10 @@ CA_DEV void unquant_fine_energy_dec(i16 *oldE, const i32 *fine_quant, RangeDec &
 }
 
 CA_DEV void unquant_energy_finalise_dec(i16 *oldE, const i32 *fine_quant, const i32 *fine_priority, int bits_left,
-                                        RangeDec &dec, int C)                                  // quant_bands.c:513
+                                        RangeDec &dec, int C, int end)                         // quant_bands.c:513
 {
     for (int prio = 0; prio < 2; prio++) {
-        for (int i = 0; i < NB && bits_left >= C; i++) {
+        for (int i = 0; i < end && bits_left >= C; i++) {
             if (fine_quant[i] >= MAX_FINE_BITS || fine_priority[i] != prio) continue;
             for (int c = 0; c < C; c++) {
                 i32 q2 = (i32)ec_dec_bits(dec, 1);
@@ -113,7 +114,7 @@ CA_DEV void unquant_energy_finalise_dec(i16 *oldE, const i32 *fine_quant, const 
     }
 }
 
-CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec)                          // celt_decoder.c:352
+CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec, int end)                 // celt_decoder.c:352
 {
     const int LM = LM3;
     u32 budget = dec.storage * 8;
@@ -122,7 +123,7 @@ CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec)          
     int tf_select_rsv = LM > 0 && tell + logp + 1 <= budget;
     budget -= tf_select_rsv;
     int tf_changed = 0, curr = 0;
-    for (int i = 0; i < NB; i++) {
+    for (int i = 0; i < end; i++) {
         if (tell + logp <= budget) {
             curr ^= ec_dec_bit_logp(dec, (u32)logp);
             tell = (u32)ec_tell(dec);
@@ -135,7 +136,7 @@ CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec)          
     const i8 *tab = CLT_tf_select_table + LM * 8;
     if (tf_select_rsv && tab[4 * isTransient + 0 + tf_changed] != tab[4 * isTransient + 2 + tf_changed])
         tf_select = ec_dec_bit_logp(dec, 1);
-    for (int i = 0; i < NB; i++) tf_res[i] = tab[4 * isTransient + 2 * tf_select + tf_res[i]];
+    for (int i = 0; i < end; i++) tf_res[i] = tab[4 * isTransient + 2 * tf_select + tf_res[i]];
 }
 
 // ---- PVQ decode ----------------------------------------------------------------------------------------
@@ -938,12 +939,13 @@ CA_DEV void negate_band_dec(x16_t *Y, int N)
     for (int j = 0; j < N; j++) Y[j] = (i16)(-Y[j]);
 }
 
-// quant_all_bands (bands.c:1337-1502), encode = 0, start 0, end 21, LM 3, C = 2
+// quant_all_bands (bands.c:1337-1502), encode = 0, start 0, LM 3; C channels (Y_ == NULL for C == 1: a band is then ONE
+// quant_band job, with one collapse mask) over the bands [0, end)
 template <class D>
 CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread, int dual_stereo, int intensity,
-                                i32 total_bits, i32 balance, int codedBands, u32 *seed)
+                                i32 total_bits, i32 balance, int codedBands, u32 *seed, const int C, const int end)
 {
-    const int LM = LM3, M = M8, C = 2;
+    const int LM = LM3, M = M8;
     const int B = shortBlocks ? M : 1;
     const i16 *eB = CLT_eband5ms;
     x16_t *X_ = F.X, *Y_ = F.X + FRAME;
@@ -954,10 +956,10 @@ CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread
     ctx.intensity = intensity;
     ctx.spread = spread;
     ctx.seed = *seed;
-    for (int i = 0; i < NB; i++) {
+    for (int i = 0; i < end; i++) {
         CA_STAMP_F(F, 14);
         ctx.i = i;
-        const int last = i == NB - 1;
+        const int last = i == end - 1;
         x16_t *X = X_ + M * eB[i], *Y = Y_ + M * eB[i];
         const int N = M * eB[i + 1] - M * eB[i];
         i32 tell = (i32)ec_tell_frac(dec);
@@ -1001,13 +1003,18 @@ CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread
         x16_t *const lo_out = last ? (x16_t *)nullptr : norm + M * eB[i];
         x16_t *const lo_out2 = last ? (x16_t *)nullptr : norm2 + M * eB[i];
         // plan the band's jobs (bands.c:1176-1335 for the stereo cases)
-        enum { DUAL = 0, STEREO = 1, STEREO_N2 = 2, DONE = 3 };
+        enum { DUAL = 0, STEREO = 1, STEREO_N2 = 2, DONE = 3, MONO = 4 };
         int kind = DUAL, njobs = 2, rebal = 0, allow2 = 0, inv = 0, sign = 1, n2_swap = 0;
         i32 mid = 0, side = 0;
         x16_t *jx0 = X, *jx1 = Y, *jl0 = lb, *jl1 = lb2, *jo0 = lo_out, *jo1 = lo_out2, *js0 = lowband_scratch, *js1 = lowband_scratch;
         int jb0 = b / 2, jb1 = b / 2, jf0 = (int)x_cm, jf1 = (int)y_cm;
         i32 jg0 = 32767, jg1 = 32767;
-        if (!dual_stereo) {
+        if (C == 1) {
+            // (quant_band_dec does the one-bin band itself)
+            kind = MONO;
+            njobs = 1;
+            jb0 = b; jf0 = (int)(x_cm | y_cm);
+        } else if (!dual_stereo) {
             if (N == 1) {
                 x_cm = y_cm = quant_band_n1_dec(dec, ctx, X, Y, lo_out);
                 kind = DONE;
@@ -1068,6 +1075,8 @@ CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread
         if (kind == DUAL) {
             x_cm = cm0;
             y_cm = cm1;
+        } else if (kind == MONO) {
+            x_cm = y_cm = cm0;
         } else if (kind == STEREO) {
             CA_STAMP_F(F, 17);
             stereo_merge_dec(X, Y, mid, N);
@@ -1099,12 +1108,12 @@ CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread
     *seed = ctx.seed;
 }
 
-// anti_collapse (bands.c:241-335), C = 2, LM = 3
+// anti_collapse (bands.c:241-335), LM = 3
 template <class D>
-CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const i16 *prev2logE, u32 seed)
+CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const i16 *prev2logE, u32 seed, const int C, const int end)
 {
-    const int LM = LM3, C = 2;
-    for (int i = 0; i < NB; i++) {
+    const int LM = LM3;
+    for (int i = 0; i < end; i++) {
         const int N0 = CLT_eband5ms[i + 1] - CLT_eband5ms[i];
         int depth = (int)((u32)(1 + F.pulses[i]) / (u32)N0) >> LM;
         i32 thresh32 = celt_exp2((i16)neg32(shl16(depth, 10 - BITRES))) >> 1;
@@ -1119,6 +1128,10 @@ CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const
         }
         for (int c = 0; c < C; c++) {
             i32 prev1 = prev1logE[c * NB + i], prev2 = prev2logE[c * NB + i];
+            if (C == 1) {
+                prev1 = imax(prev1, prev1logE[NB + i]);
+                prev2 = imax(prev2, prev2logE[NB + i]);
+            }
             i32 Ediff = (i32)logE[c * NB + i] - imin(prev1, prev2);
             Ediff = imax(0, Ediff);
             i32 r;
@@ -1147,13 +1160,12 @@ CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const
     }
 }
 
-// denormalise_bands (bands.c:169-238) for one channel, start 0, end 21, downsample 1; lanes share a band's bins
-// denormalise_bands (bands.c:169-239), start 0, end 21, M = 8, no downsampling. The reference walks the bands; a wavefront doing
+// denormalise_bands (bands.c:169-239) for one channel, start 0, M = 8, no downsampling; zeros from the end band's edge on. The reference walks the bands; a wavefront doing
 // that pays 21 dependent steps (the band's energy from HBM, then its 8-176 bins, a sixth of the lanes busy on the narrow bands).
 // Here the 21 gains are computed side by side (one lane per band), and the 960 bins are then walked 64 at a time with all of a
 // lane's loads issued together; a bin finds its band through a 120-entry table (bands start at multiples of eight bins).
 template <class S>
-CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int silence)
+CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int silence, int end)
 {
     const int N = FRAME;
     i32 *freq = L.freq;
@@ -1179,7 +1191,7 @@ CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int s
         wave_sync();
         return;
     }
-    const int bound = M8 * CLT_eband5ms[NB];
+    const int bound = M8 * CLT_eband5ms[end];                   // zeros above the packet's end band (bands.c:179, :237)
     if (LANES == 64) {
         i32 xv[(FRAME + 63) / 64];
 #pragma unroll
@@ -1255,11 +1267,30 @@ CA_DEV void comb_filter_inplace_dec(i32 *x, int T0, int T1, int N, i32 g0, i32 g
 
 struct DecResult { int samples; u32 final_range; };
 
-// Stage 1 of opus_decode() of one CELT-only 20 ms stereo packet (code 0; data: the whole packet incl. TOC):
+// The TOC bytes this decoder takes (src/opus_decoder.c, opus_packet_parse_impl): CELT-only (0x80), 20 ms (3 << 3), code 0, any of
+// the four audio bandwidths (bits 5-6: NB, WB, SWB, FB) and mono or stereo (bit 2): 0x98 0xB8 0xD8 0xF8 / 0x9C 0xBC 0xDC 0xFC
+CA_DEV bool celt_toc_accepted(int toc) { return (toc & 0x9B) == 0x98; }
+CA_DEV int celt_toc_end(int toc) { const int bw = (toc >> 5) & 3; return bw == 0 ? 13 : bw == 1 ? 17 : bw == 2 ? 19 : 21; }   // src/opus_decoder.c:431-448
+CA_DEV int celt_toc_channels(int toc) { return (toc & 4) ? 2 : 1; }
+// what the stream remembers of its last TOC; the zeros of a fresh state read as fullband stereo (st->bandwidth == 0)
+CA_DEV int celt_state_end(const opusgpu_celt_dec_state *st) { const int e = st->last_end; return e == 13 || e == 17 || e == 19 ? e : NB; }
+CA_DEV int celt_state_channels(const opusgpu_celt_dec_state *st) { return st->last_channels == 1 ? 1 : 2; }
+// src/opus_decoder.c:683-686: st->bandwidth / st->stream_channels follow every packet's TOC, a one-byte (DTX) packet's too
+CA_DEV void celt_state_note_toc(opusgpu_celt_dec_state *st, int toc)
+{
+    const int end = celt_toc_end(toc), C = celt_toc_channels(toc);
+    if (C != celt_state_channels(st)) CA_COUNT(C == 1 ? "chbw_stereo_to_mono" : "chbw_mono_to_stereo", 1);
+    st->last_end = end;
+    st->last_channels = C;
+}
+
+// Stage 1 of opus_decode() of one CELT-only 20 ms packet (code 0; data: the whole packet incl. TOC):
 // everything up to the normalised bands (one lane per stream). Leaves X and the frame parameters in the state's
 // hand-off fields; st->mid_valid == 0 tells the later stages to leave this stream alone.
-template <class D>
-CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
+// FBS: the caller knows the packet to be fullband stereo (TOC 0xFC); C and end are then the compile-time constants they were
+// before the other TOCs were taken, which is what the lane kernel runs when its whole wavefront holds such packets.
+template <bool FBS, class D>
+CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
 {
     DecResult res;
     res.samples = OPUSGPU_INVALID_PACKET;
@@ -1267,16 +1298,23 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     st->mid_valid = 0;
     F.X = (x16_t *)st->mid_X;
     F.norm = (x16_t *)st->mid_norm;
-    const int C = 2, N = FRAME, LM = LM3, M = M8;
-    if (len < 2) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }   // len == 1: PLC/DTX, not implemented
-    // TOC (src/opus_decoder.c, opus_packet_parse_impl): CELT-only (0x80), fullband (3 << 5), 20 ms (3 << 3), stereo (4), code 0
-    if (data[0] != 0xFC) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
+    const int N = FRAME, LM = LM3, M = M8;
+    if (len < 2) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }   // len == 1: DTX, the PLC entry point's business
+    const int toc = data[0];
+    if (!celt_toc_accepted(toc)) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
     data++;
     len--;
     if (len > 1275) { res.samples = OPUSGPU_INVALID_PACKET; return res; }
+    const int C = FBS ? 2 : celt_toc_channels(toc), end = FBS ? (int)NB : celt_toc_end(toc);
+    celt_state_note_toc(st, toc);
+    CA_COUNT(end == 13 ? "chbw_end13" : end == 17 ? "chbw_end17" : end == 19 ? "chbw_end19" : "chbw_end21", 1);
     RangeDec dec;
     ec_dec_init(dec, data, (u32)len);
     i16 *oldBandE = st->oldBandE, *oldLogE = st->oldLogE, *oldLogE2 = st->oldLogE2, *backgroundLogE = st->backgroundLogE;
+    if (C == 1) {                                                                               // celt_decoder.c:841-845
+        CA_COUNT("chbw_mono", 1);
+        for (int i = 0; i < NB; i++) oldBandE[i] = (i16)imax(oldBandE[i], oldBandE[NB + i]);
+    }
 
     i32 total_bits = len * 8;
     i32 tell = ec_tell(dec);
@@ -1308,9 +1346,9 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     const int shortBlocks = isTransient ? M : 0;
     const int intra_ener = tell + 3 <= total_bits ? ec_dec_bit_logp(dec, 3) : 0;
     CA_STAMP_F(F, 0);
-    unquant_coarse_energy_dec(oldBandE, intra_ener, dec, C);
+    unquant_coarse_energy_dec(oldBandE, intra_ener, dec, C, end);
     CA_STAMP_F(F, 1);
-    tf_decode_dec(isTransient, F.tf_res, dec);
+    tf_decode_dec(isTransient, F.tf_res, dec, end);
     tell = ec_tell(dec);
     int spread_decision = SPREAD_NORMAL;
     if (tell + 4 <= total_bits) spread_decision = ec_dec_icdf(dec, CLT_spread_icdf, 5);
@@ -1321,7 +1359,7 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     int dynalloc_logp = 6;
     total_bits <<= BITRES;
     tell = (i32)ec_tell_frac(dec);
-    for (int i = 0; i < NB; i++) {
+    for (int i = 0; i < end; i++) {
         int width = C * (CLT_eband5ms[i + 1] - CLT_eband5ms[i]) << LM;
         int quanta = imin(width << BITRES, imax(6 << BITRES, width));
         int dynalloc_loop_logp = dynalloc_logp, boost = 0;
@@ -1340,26 +1378,32 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     i32 bits = ((len * 8) << BITRES) - (i32)ec_tell_frac(dec) - 1;
     const int anti_collapse_rsv = isTransient && LM >= 2 && bits >= ((LM + 2) << BITRES) ? (1 << BITRES) : 0;
     bits -= anti_collapse_rsv;
-    AllocOut al = compute_allocation_wave(F, dec, C, alloc_trim, 0, 0, bits, 0, 0);
-    unquant_fine_energy_dec(oldBandE, F.fine_quant, dec, C);
+    AllocOut al = compute_allocation_wave(F, dec, C, alloc_trim, 0, 0, bits, 0, 0, end);
+    unquant_fine_energy_dec(oldBandE, F.fine_quant, dec, C, end);
     CA_STAMP_F(F, 2);
 
     u32 rng = st->rng;
     quant_all_bands_dec(F, dec, shortBlocks, spread_decision, al.dual_stereo, al.intensity,
-                        len * (8 << BITRES) - anti_collapse_rsv, al.balance, al.codedBands, &rng);
+                        len * (8 << BITRES) - anti_collapse_rsv, al.balance, al.codedBands, &rng, C, end);
     st->rng = rng;
     CA_STAMP_F(F, 10);
     int anti_collapse_on = 0;
     if (anti_collapse_rsv > 0) anti_collapse_on = (int)ec_dec_bits(dec, 1);
-    unquant_energy_finalise_dec(oldBandE, F.fine_quant, F.fine_priority, len * 8 - ec_tell(dec), dec, C);
-    if (anti_collapse_on) anti_collapse_dec(F, oldBandE, oldLogE, oldLogE2, st->rng);
-    if (silence)
+    unquant_energy_finalise_dec(oldBandE, F.fine_quant, F.fine_priority, len * 8 - ec_tell(dec), dec, C, end);
+    if (anti_collapse_on) {
+        if (C == 1) CA_COUNT("chbw_mono_anti_collapse", 1);
+        anti_collapse_dec(F, oldBandE, oldLogE, oldLogE2, st->rng, C, end);
+    }
+    if (silence) {
+        if (C == 1) CA_COUNT("chbw_mono_silence", 1);
         for (int i = 0; i < C * NB; i++) oldBandE[i] = -28672;
+    }
 
     // hand the frame over to the synthesis and post-filter stages
     st->mid_valid = 1;
     st->mid_isTransient = isTransient;
     st->mid_silence = silence;
+    st->mid_mono = C == 1;
     st->postfilter_period = imax(st->postfilter_period, MINP);
     st->postfilter_period_old = imax(st->postfilter_period_old, MINP);
     st->mid_pf_period_old = st->postfilter_period_old; st->mid_pf_period = st->postfilter_period; st->mid_pf_period_new = postfilter_pitch;
@@ -1372,6 +1416,8 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     st->postfilter_gain_old = st->postfilter_gain;
     st->postfilter_tapset_old = st->postfilter_tapset;
 
+    if (C == 1)                                                                                  // celt_decoder.c:1027-1028
+        for (int i = 0; i < NB; i++) oldBandE[NB + i] = oldBandE[i];
     if (!isTransient) {
         if (st->loss_count >= 10) CA_COUNT("plc_recover_after_10", 1);
         for (int i = 0; i < 2 * NB; i++) { oldLogE2[i] = oldLogE[i]; oldLogE[i] = oldBandE[i]; }
@@ -1380,6 +1426,11 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     } else {
         for (int i = 0; i < 2 * NB; i++) oldLogE[i] = (i16)imin(oldLogE[i], oldBandE[i]);
     }
+    for (int c = 0; c < 2; c++)                                                                  // celt_decoder.c:1049-1061 (start == 0)
+        for (int i = end; i < NB; i++) {
+            oldBandE[c * NB + i] = 0;
+            oldLogE[c * NB + i] = oldLogE2[c * NB + i] = -28672;
+        }
     st->rng = dec.rng;
 
     st->loss_count = 0;
@@ -1392,14 +1443,23 @@ CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *d
     return res;
 }
 
-// Stage 2 (one wavefront per stream; LANES == 1 in the emulation): celt_synthesis (celt_decoder.c:287-350) for
-// C == CC == 2 -- shift the history, denormalise, inverse MDCT with TDAC into decode_mem.
+template <class D>
+CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
+{
+    return celt_decode_front_as<false>(F, st, data, len);
+}
+
+// Stage 2 (one wavefront per stream; LANES == 1 in the emulation): celt_synthesis (celt_decoder.c:287-350) for CC == 2 -- shift the
+// history, denormalise up to the frame's end band, inverse MDCT with TDAC into decode_mem. A mono frame (C == 1, :313-325) is ONE
+// spectrum that goes into both channels' decode_mem (their overlap tails differ after a stereo frame): both passes below then
+// read channel 0's bands and energies.
 template <class S>
 CA_DEV void celt_decode_synth(S &L, opusgpu_celt_dec_state *st)
 {
     if (!uni(st->mid_valid)) return;
     const int N = FRAME;
     const int isTransient = uni(st->mid_isTransient), silence = uni(st->mid_silence);
+    const int mono = uni(st->mid_mono), end = uni(celt_state_end(st));
     // OPUS_MOVE(decode_mem, decode_mem + N, DECODE_BUFFER_SIZE - N + overlap/2) of both channels first
     if (LANES == 64) {
         // the whole move through registers, 16 bytes per lane and access: the ten loads of the two channels, then their ten
@@ -1442,7 +1502,7 @@ CA_DEV void celt_decode_synth(S &L, opusgpu_celt_dec_state *st)
     for (int c = 0; c < 2; c++) {
         i32 *mem = st->decode_mem[c];
         i32 *out_syn = mem + DEC_BUF - N;
-        denormalise_bands_dec(L, st->mid_X + c * N, st->oldBandE + c * NB, silence);
+        denormalise_bands_dec(L, st->mid_X + (mono ? 0 : c * N), st->oldBandE + (mono ? 0 : c * NB), silence, end);
         if (isTransient) {
             const MdctTab T = mdct_global_tab<3>();
             mdct_backward_wave<3, 8>(L.freq, 1, L.f2, out_syn, T, lane());

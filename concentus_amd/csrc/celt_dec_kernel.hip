@@ -1,4 +1,4 @@
-// celt_dec_kernel.hip -- batched opus_decode() for CELT-only 20 ms stereo packets, one lane per stream.
+// celt_dec_kernel.hip -- batched opus_decode() for CELT-only 20 ms packets (mono or stereo, NB / WB / SWB / FB), one lane per stream.
 //
 // Replaces opus_decode() (opus-fix/src/opus_decoder.c:758; include/opus.h:462) -> opus_decode_native ->
 // opus_decode_frame -> celt_decode_with_ec (celt/celt_decoder.c:713) for N streams at once. Decoding a
@@ -20,7 +20,7 @@ namespace ca {
 
 // A = streams per wavefront (64, or 32 / 16 with 2 / 4 partly filled waves per 64-stream workgroup; see
 // celt_back_lane_kernel.hip)
-// PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is the one-byte DTX packet is left to
+// PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is a one-byte DTX packet is left to
 // the concealment kernels (celt_dec_plc_kernel.hip), which find it by st->mid_plc
 template <int A, bool PLC>
 __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu_celt_dec_state *states, const u8 *__restrict__ packets,
@@ -38,9 +38,12 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
     F.lds_pvq16 = (CA_AS_LDS i16 *)(g_lds_pvq16 + slot);
     const int ln = PLC && !len ? 0 : len[k];
     if (PLC) {
-        const bool lost = ln == 0 || (ln == 1 && packet_stride >= 1 && packets[(size_t)k * packet_stride] == 0xFC);
+        const int toc = ln == 1 && packet_stride >= 1 ? packets[(size_t)k * packet_stride] : -1;
+        const bool dtx = toc >= 0 && celt_toc_accepted(toc);
+        const bool lost = ln == 0 || dtx;
         states[k].mid_plc = lost ? OPUSGPU_PLC_LOST : OPUSGPU_PLC_NONE;
         if (lost) {
+            if (dtx) celt_plc_dtx_toc(states + k, toc);
             states[k].mid_valid = 0;
             ret[k] = FRAME;
             rng[k] = 0;
@@ -54,7 +57,14 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
         rng[k] = 0;
         return;
     }
-    DecResult r = celt_decode_front(F, states + k, packets + (size_t)k * packet_stride, ln);
+    // The streams of a wavefront may differ in channel count and bandwidth, so both are run-time values of the lane -- unless
+    // every stream still in this wavefront holds a fullband stereo packet: then the instantiation with both fixed runs, which is
+    // the code the received-only fullband-stereo batch ran before the other TOCs were taken (3.07 ms against 3.15 ms for 65 536).
+    const u8 *pkt = packets + (size_t)k * packet_stride;
+    const bool other = ln < 2 || pkt[0] != 0xFC;
+    DecResult r;
+    if (__builtin_amdgcn_ballot_w64(other) == 0) r = celt_decode_front_as<true>(F, states + k, pkt, ln);
+    else r = celt_decode_front_as<false>(F, states + k, pkt, ln);
     ret[k] = r.samples;
     rng[k] = r.final_range;
 }
@@ -185,7 +195,7 @@ __global__ __launch_bounds__(64) void quant_all_bands_dec_hook_kernel(opusgpu_qa
     load(dec, rec->ec);
     u32 seed = rec->seed;
     quant_all_bands_dec(F, dec, rec->shortBlocks, rec->spread, rec->dual_stereo, rec->intensity, rec->total_bits, rec->balance,
-                        rec->codedBands, &seed);
+                        rec->codedBands, &seed, 2, NB);
     for (int k = 0; k < 2 * NB; k++) rec->collapse_masks[k] = F.collapse_masks[k];
     rec->seed = seed;
     store(rec->ec, dec);

@@ -81,14 +81,14 @@ CA_DEV u32 pvq_u(int n, int k)                                                  
     return CLT_pvq_u_data[CLT_pvq_u_row[lo] + hi];
 }
 
-// ---- compute_allocation (rate.c:527-639 + :248-525), start 0, end 21, LM 3, encode 1 ---------------
+// ---- compute_allocation (rate.c:527-639 + :248-525), start 0, LM 3; end 21 unless the decoder passes its packet's ----
 struct AllocOut { int codedBands; i32 balance; int intensity; int dual_stereo; };
 
 template <class L, class EC>
 CA_DEVFN AllocOut compute_allocation_wave(L &F, EC &ec, int C, int alloc_trim, int intensity_in,
-                                          int dual_stereo_in, i32 total, int prev, int signalBandwidth)
+                                          int dual_stereo_in, i32 total, int prev, int signalBandwidth, const int end = NB)
 {
-    const int LM = LM3, end = NB, start = 0, len = NB;
+    const int LM = LM3, start = 0, len = NB;
     const i16 *eB = CLT_eband5ms;
     i32 *bits = F.pulses, *ebits = F.fine_quant, *fine_priority = F.fine_priority;
     AllocOut out;

@@ -309,15 +309,20 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
         // noise-based PLC/CNG (celt_decoder.c:451-506): decay the energies toward the background, fill the bands with noise;
         // celt_synthesis is celt_decode_synth, fed through the hand-off
         CA_COUNT("plc_noise", 1);
+        // both channels of the decoder, the bands [0, end) of the last packet's bandwidth (st->end); the synthesis zeroes the rest
+        const int end = uni(celt_state_end(st));
+        if (end < NB) CA_COUNT("chbw_plc_noise_narrow", 1);
         const i32 decay = loss_count == 0 ? 1536 : 512;                            // QCONST16(1.5f / .5f, DB_SHIFT)
         const u32 seed0 = uni(st->rng);
-        for (int i = lane(); i < 2 * NB; i += LANES) st->oldBandE[i] = (i16)imax(st->backgroundLogE[i], st->oldBandE[i] - decay);
-        // one lane per (channel, band): the band's first draw is (channel * 800 + its first bin) steps down the chain
+        for (int i = lane(); i < 2 * NB; i += LANES)
+            if (i % NB < end) st->oldBandE[i] = (i16)imax(st->backgroundLogE[i], st->oldBandE[i] - decay);
+        // one lane per (channel, band): the band's first draw is (channel * M * eBands[end] + its first bin) steps down the chain
         for (int b = lane(); b < 2 * NB; b += LANES) {
             const int c = b >= NB, i = b - c * NB;
+            if (i >= end) continue;
             const int first = M8 * CLT_eband5ms[i], blen = M8 * (CLT_eband5ms[i + 1] - CLT_eband5ms[i]);
             x16_t *X = (x16_t *)st->mid_X + c * FRAME + first;
-            u32 seed = plc_lcg_jump(seed0, c * M8 * CLT_eband5ms[NB] + first);
+            u32 seed = plc_lcg_jump(seed0, c * M8 * CLT_eband5ms[end] + first);
             for (int j = 0; j < blen; j++) {
                 seed = celt_lcg_rand(seed);
                 X[j] = (i16)((i32)seed >> 20);
@@ -326,10 +331,11 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
         }
         wave_sync();
         if (lane() == 0) {
-            st->rng = plc_lcg_jump(seed0, 2 * M8 * CLT_eband5ms[NB]);
+            st->rng = plc_lcg_jump(seed0, 2 * M8 * CLT_eband5ms[end]);
             st->mid_valid = 1;
             st->mid_isTransient = 0;
             st->mid_silence = 0;
+            st->mid_mono = 0;
             st->mid_pf_period_old = st->mid_pf_period = st->mid_pf_period_new = MINP;   // no post-filter on a concealed frame
             st->mid_pf_gain_old = st->mid_pf_gain = st->mid_pf_gain_new = 0;
             st->mid_pf_tapset_old = st->mid_pf_tapset = st->mid_pf_tapset_new = 0;
@@ -524,13 +530,39 @@ CA_DEV void celt_deemphasis_channel(opusgpu_celt_dec_state *st, int c, i16 *pcm)
 }
 
 // which packets opusgpu_decode_batch_plc conceals: a lost one (no length) and DTX, a packet that is nothing but the TOC byte
-// (src/opus_decoder.c:246-251); only the TOC of the one configuration this decoder implements
-CA_DEV bool celt_plc_conceals(const u8 *data, int len) { return len == 0 || (len == 1 && data[0] == 0xFC); }
+// (src/opus_decoder.c:246-251); only the TOCs this decoder implements. The stream takes such a TOC's bandwidth and channel
+// count before it is concealed (celt_plc_dtx_toc).
+CA_DEV bool celt_plc_conceals(const u8 *data, int len);
+
+CA_DEV void celt_plc_dtx_toc(opusgpu_celt_dec_state *st, int toc)
+{
+    if (celt_toc_end(toc) != celt_state_end(st)) CA_COUNT("chbw_dtx_end_change", 1);
+    celt_state_note_toc(st, toc);
+}
+
+#if defined(CA_HOST_EMU)
+// The emulation asks celt_plc_conceals(data, len) and then calls celt_decode_lost_frame(P, L, st, pcm), which does not see the
+// packet: the TOC of a DTX packet travels between the two calls here (the emulation is one thread).
+static int g_emu_dtx_toc = -1;
+#endif
+
+CA_DEV bool celt_plc_conceals(const u8 *data, int len)
+{
+    const bool dtx = len == 1 && celt_toc_accepted(data[0]);
+#if defined(CA_HOST_EMU)
+    g_emu_dtx_toc = dtx ? data[0] : -1;
+#endif
+    return len == 0 || dtx;
+}
 
 // a lost frame through all stages, for the host emulation
 template <class LP_, class S>
 CA_DEV DecResult celt_decode_lost_frame(LP_ &P, S &L, opusgpu_celt_dec_state *st, i16 *pcm)
 {
+#if defined(CA_HOST_EMU)
+    if (g_emu_dtx_toc >= 0) celt_plc_dtx_toc(st, g_emu_dtx_toc);
+    g_emu_dtx_toc = -1;
+#endif
     st->mid_valid = 0;
     st->mid_plc = OPUSGPU_PLC_LOST;
     celt_plc_wave(P, st);

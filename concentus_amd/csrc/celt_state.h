@@ -59,7 +59,10 @@ typedef struct opusgpu_celt_state {
  * stream (opus-fix/celt/celt_decoder.c:66-97 and the trailing arrays :94-96). `lpc` and `last_pitch_index`
  * belong to the packet loss concealment (celt_decode_lost, celt_plc.h): the synthesis filter of the first lost
  * frame and its pitch, reused by the losses that follow it. `started` is the Opus layer's "prev_mode != 0"
- * (src/opus_decoder.c:259-268): set by every decoded packet, cleared by init/reset; a loss before it is zeros. */
+ * (src/opus_decoder.c:259-268): set by every decoded packet, cleared by init/reset; a loss before it is zeros.
+ * `last_end` and `last_channels` are the Opus layer's st->bandwidth and st->stream_channels as the CELT decoder sees them
+ * (src/opus_decoder.c:431-450, :683-686): the end band (13, 17, 19, 21) and the channel count (1, 2) of the last packet's TOC,
+ * which a lost packet is concealed with. 0 (init / reset) reads as 21 / stereo. */
 #define OPUSGPU_DECODE_BUFFER_SIZE 2048
 #define OPUSGPU_CELT_LPC_ORDER 24
 typedef struct opusgpu_celt_dec_state {
@@ -72,7 +75,8 @@ typedef struct opusgpu_celt_dec_state {
     int32_t loss_count;
     int32_t last_pitch_index;
     int32_t started;
-    int32_t reserved[3];
+    int32_t last_end, last_channels;
+    int32_t reserved[1];
     int16_t oldBandE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE2[2 * OPUSGPU_CELT_NBANDS];
@@ -83,7 +87,7 @@ typedef struct opusgpu_celt_dec_state {
      * bands, what the synthesis and post-filter kernels need to know about the frame, and the per-stream result */
     int16_t mid_X[2 * OPUSGPU_CELT_FRAME];
     int16_t mid_norm[2 * 624];                             /* the frame's folding source (bands.c norm / norm2): working storage of the lane kernel */
-    int32_t mid_valid, mid_isTransient, mid_silence;
+    int32_t mid_valid, mid_isTransient, mid_silence;               /* (the frame's end band is last_end) */
     int32_t mid_pf_period_old, mid_pf_period, mid_pf_period_new;
     int32_t mid_pf_gain_old, mid_pf_gain, mid_pf_gain_new;
     int32_t mid_pf_tapset_old, mid_pf_tapset, mid_pf_tapset_new;
@@ -91,7 +95,7 @@ typedef struct opusgpu_celt_dec_state {
      * S1 of the signal whose excitation the pitch-based branch copied (celt_decoder.c:629-634), per channel */
     int32_t mid_plc;
     int32_t mid_plc_S1[2];
-    int32_t mid_pad;
+    int32_t mid_mono;                                      /* the frame is one coded channel, synthesised into both (celt_decoder.c:313-325) */
 } opusgpu_celt_dec_state;
 
 /* mid_plc: the stream was received / is lost and not yet looked at / has no history (zeros) / is synthesised from noise by
@@ -106,6 +110,8 @@ typedef struct opusgpu_celt_dec_state {
 /* the synthesis kernel moves decode_mem in 16-byte units, and the records of a batch lie back to back */
 static_assert(offsetof(opusgpu_celt_dec_state, decode_mem) % 16 == 0, "decode_mem must stay 16-byte aligned");
 static_assert(sizeof(opusgpu_celt_dec_state) % 16 == 0, "sizeof(opusgpu_celt_dec_state) must stay a multiple of 16");
+static_assert(offsetof(opusgpu_celt_dec_state, last_end) == 52 && offsetof(opusgpu_celt_dec_state, oldBandE) == 64,
+              "last_end / last_channels took two of the reserved words: no offset may move");
 #endif
 
 #ifdef __cplusplus

@@ -191,6 +191,7 @@ struct OpusGpuDecoder {
     int16_t *d_pcm;
     uint32_t final_range;
     int last_packet_duration;
+    int bandwidth;                 // OPUS_BANDWIDTH_* of the last decoded packet's TOC; 0: none since create / reset
     hipStream_t stream;
 };
 
@@ -250,7 +251,8 @@ extern "C" int opusgpu_decoder_ctl(OpusGpuDecoder *st, int request, ...)
     case 4009: case 4029: case 4039: case 4045: {                                 // getters (src/opus_decoder.c:828-938)
         int32_t *p = va_arg(ap, int32_t *);
         if (!p) ret = OPUSGPU_BAD_ARG;
-        else *p = request == 4009 ? 1105 : request == 4029 ? 48000 : request == 4039 ? st->last_packet_duration : 0;
+        // OPUS_GET_BANDWIDTH: the last packet's; before the first packet FULLBAND (the reference answers 0 there)
+        else *p = request == 4009 ? (st->bandwidth ? st->bandwidth : 1105) : request == 4029 ? 48000 : request == 4039 ? st->last_packet_duration : 0;
         break;
     }
     case 4034:                                                                    // OPUS_SET_GAIN: only 0 dB
@@ -260,6 +262,7 @@ extern "C" int opusgpu_decoder_ctl(OpusGpuDecoder *st, int request, ...)
         ret = opusgpu_celt_dec_state_init(st->d_state, 1, st->stream);
         st->final_range = 0;
         st->last_packet_duration = 0;
+        st->bandwidth = 0;
         break;
     default: ret = OPUSGPU_UNIMPLEMENTED;
     }
@@ -286,6 +289,8 @@ extern "C" int opusgpu_decode(OpusGpuDecoder *st, const unsigned char *data, int
         return OPUSGPU_INTERNAL_ERROR;
     if (ret > 0) {
         st->last_packet_duration = ret;
+        static const int bw[4] = {1101, 1103, 1104, 1105};                       // CELT-only TOC, bits 5-6: NB, WB, SWB, FB
+        st->bandwidth = bw[(data[0] >> 5) & 3];
         if (hipMemcpy(pcm, st->d_pcm, (size_t)ret * 2 * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) return OPUSGPU_INTERNAL_ERROR;
     }
     return ret;

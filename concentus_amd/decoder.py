@@ -30,8 +30,12 @@ class OpusDecoderBatch:
     def decode(self, packets, lengths, conceal=False):
         """opus_decode(dec, data, len, pcm, 960, 0) for every stream: packets uint8 [N][stride], lengths int32 [N].
         Returns (pcm int16 [N][960][2], ret int32 [N] = 960 or a negative error per stream).
+        Accepted are CELT-only 20 ms single-frame packets, mono or stereo, NB / WB / SWB / FB (TOC 0x98 0xB8 0xD8 0xF8 /
+        0x9C 0xBC 0xDC 0xFC), in any mix over the streams and over time; a mono packet comes out on both channels. Any other
+        TOC gives that stream -5.
         conceal=True (opusgpu_decode_batch_plc): a stream with length 0 lost its packet and is concealed
-        (opus_decode(dec, NULL, 0, ...)), as is a one-byte DTX packet; its ret is 960 and its final range 0."""
+        (opus_decode(dec, NULL, 0, ...)) within the bandwidth of its last packet, as is a one-byte DTX packet with one of
+        those TOCs, whose bandwidth the stream takes first; its ret is 960 and its final range 0."""
         import torch
         if packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[0] != self.n or not packets.is_contiguous():
             raise ValueError("packets must be a contiguous uint8 tensor [streams][stride]")
@@ -68,7 +72,8 @@ class OpusDecoderBatch:
 
 
 def decode_independent(packets, lengths):
-    """Decode every packet with its own fresh decoder (the first packet of its own stream)."""
+    """Decode every packet with its own fresh decoder (the first packet of its own stream); the packets may differ in
+    channel count and bandwidth (the TOCs of OpusDecoderBatch.decode)."""
     dec = OpusDecoderBatch(packets.shape[0], device=packets.device)
     pcm, ret = dec.decode(packets, lengths)
     return pcm, ret, dec.final_range

@@ -154,8 +154,17 @@ int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_states, const i
 
 /* ---- batched opus_decode(), CELT-only ------------------------------------------------------------------
  * Replaces, for N streams at once, opus_decode() (opus-fix/src/opus_decoder.c:758, include/opus.h:462) ->
- * opus_decode_native -> opus_decode_frame -> celt_decode_with_ec (celt/celt_decoder.c:713) for packets with
- * TOC 0xFC (CELT-only, fullband, 20 ms, stereo, one frame). One call decodes the next packet of every stream:
+ * opus_decode_native -> opus_decode_frame -> celt_decode_with_ec (celt/celt_decoder.c:713) for CELT-only 20 ms
+ * packets of one frame (code 0), mono or stereo, at any of the four CELT audio bandwidths -- these eight TOC bytes:
+ *
+ *                              NB (end band 13)  WB (17)  SWB (19)  FB (21)
+ *     mono packet   (C = 1)         0x98          0xB8      0xD8     0xF8
+ *     stereo packet (C = 2)         0x9C          0xBC      0xDC     0xFC
+ *
+ * decoded as opus_decode() does on a decoder made with opus_decoder_create(48000, 2): a mono packet comes out on both
+ * channels, and the streams of one call may differ in TOC and change it from packet to packet. Every other TOC (SILK,
+ * hybrid, codes 1-3, other frame sizes) gives that stream OPUSGPU_UNIMPLEMENTED, as does a one-byte packet here. One
+ * call decodes the next packet of every stream:
  *   d_states   device, n x opusgpu_celt_dec_state_size() bytes, initialised once with
  *              opusgpu_celt_dec_state_init (== opus_decoder_create(48000, 2)); advanced by one frame per call.
  *   d_packets  device, packet i at d_packets + i * packet_stride, d_len[i] bytes (as opus_decode's data, len).
@@ -172,7 +181,8 @@ int opusgpu_decode_batch(void *d_states, const unsigned char *d_packets, int pac
 /* The same call with packet loss concealment (celt_decode_lost, celt/celt_decoder.c:395-711, bit-exact): the arguments of
  * opusgpu_decode_batch, and
  *   d_len[i] == 0                  stream i lost its packet: opus_decode(st, NULL, 0, pcm, 960, 0);
- *   d_len[i] == 1 with TOC 0xFC    DTX, concealed in the same way (src/opus_decoder.c:246-251); other one-byte packets
+ *   d_len[i] == 1, TOC as above    DTX, concealed in the same way (src/opus_decoder.c:246-251) after the stream has taken the
+ *                                  TOC's bandwidth and channel count (:683-686); other one-byte packets
  *                                  return OPUSGPU_UNIMPLEMENTED;
  *   d_len == NULL                  every stream is lost; d_packets may then be NULL.
  * A concealed stream reports d_ret = 960 and d_rng = 0; one that has not decoded a packet yet gets 960 zero samples and keeps
@@ -195,8 +205,11 @@ int opusgpu_encoder_ctl(OpusGpuEncoder *st, int request, ...);
 int32_t opusgpu_encode(OpusGpuEncoder *st, const int16_t *pcm, int frame_size, unsigned char *data, int32_t max_data_bytes);
 void opusgpu_encoder_destroy(OpusGpuEncoder *st);
 /* Decoder side, likewise: opus_decoder_create / opus_decode / opus_decoder_ctl / opus_decoder_destroy
- * (opus-fix/include/opus.h:438-505; src/opus_decoder.c:121, :758, :788, :911) for 48 kHz stereo and CELT-only
- * 20 ms stereo packets; ctl: OPUS_GET_FINAL_RANGE, OPUS_GET_LAST_PACKET_DURATION, OPUS_RESET_STATE. opusgpu_decode itself
+ * (opus-fix/include/opus.h:438-505; src/opus_decoder.c:121, :758, :788, :911) for a 48 kHz stereo decoder and the eight
+ * CELT-only 20 ms TOCs of opusgpu_decode_batch (0x98 0xB8 0xD8 0xF8 mono, 0x9C 0xBC 0xDC 0xFC stereo); ctl:
+ * OPUS_GET_FINAL_RANGE, OPUS_GET_LAST_PACKET_DURATION, OPUS_RESET_STATE, and OPUS_GET_BANDWIDTH = the last decoded packet's
+ * bandwidth (1101, 1103, 1104, 1105) -- before the first packet and after a reset it answers 1105, where the reference
+ * answers 0. opusgpu_decode itself
  * returns OPUS_UNIMPLEMENTED for data == NULL / decode_fec; a lost packet goes through opusgpu_decode_lost, which is
  * opus_decode(st, NULL, 0, pcm, frame_size, 0): 960 for frame_size 960 (afterwards the last packet duration is 960 and the
  * final range 0), OPUS_UNIMPLEMENTED for any other multiple of 120, OPUS_BAD_ARG otherwise. The libopus-named opus_decode of
