@@ -22,7 +22,7 @@
 // map still points at it).
 // sLPC_Q14[0..32) of the state output is rebuilt from the winner's Xq ring: after the last subframe (length >= 32)
 // both hold the last 32 xq_Q14 values (:307).
-#include "silk_math.h"
+#include "silk_nsq_dev.h"
 #include "opusgpu_internal.h"
 #include "../../include/opusgpu_silk.h"
 #include "silk_validate.h"
@@ -35,7 +35,6 @@ enum { DELAY = 32, MASK = 31, R_RND = 0, R_Q = 32, R_XQ = 64, R_PRED = 96, R_SHA
 // walked by the four lanes of a quad (the survivor copy) both spread over the banks. 160 rows x 256 B = 40 KB per
 // wavefront, four workgroups per CU.
 CA_DEV int ridx(int row, int lanecol) { return row * 64 + ((lanecol + row) & 63); }
-struct Scratch { i32 sLTP_Q15[640]; i16 sLTP[640]; };
 struct Cand { i32 q, rd, xq, lf_ar, shp, exc; };
 
 // value of quad lane J (compile-time) / j (run-time, quad-uniform) in every lane of the quad
@@ -62,7 +61,7 @@ CA_DEV i16 sat16(i32 v) { return (i16)(v > 32767 ? 32767 : (v < -32768 ? -32768 
 }  // namespace dd
 
 __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_dd_in *__restrict__ recs, opusgpu_nsq_state *states,
-                                                              opusgpu_nsq_dd_out *__restrict__ outs, dd::Scratch *ws, int n_rec,
+                                                              opusgpu_nsq_dd_out *__restrict__ outs, NsqScratch *ws, int n_rec,
                                                               int *__restrict__ bad_records, const int *__restrict__ rows)
 {
     using namespace dd;
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
     ring[ridx(R_SHAPE + 0, ln)] = NSQ.sLTP_shp_Q14[ltp_mem - 1];
     i32 prev_gain_Q16 = NSQ.prev_gain_Q16;
     int lag = NSQ.lagPrev;
-    const int offset_Q10 = voiced ? (in.quantOffsetType ? 100 : 32) : (in.quantOffsetType ? 240 : 100);   // silk/tables_other.c:95-97
+    const int offset_Q10 = nsq_offset_Q10(in.signalType, in.quantOffsetType);
     int smpl = 0;
     int delay = L < DELAY ? L : DELAY;
     if (voiced) {
@@ -118,8 +117,7 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
         const i32 *x_Q3 = &in.x_Q3[sf * L];
         i8 *pl = pulses + sf * L;
         i16 *pxq = &NSQ.xq[ltp_mem + sf * L];
-        i32 harm = in.HarmShapeGain_Q14[sf] >> 2;
-        harm |= shl32(in.HarmShapeGain_Q14[sf] >> 1, 16);
+        const i32 harm = nsq_harm_packed_Q14(in.HarmShapeGain_Q14[sf]);
         rewhite = 0;
         if (voiced) {
             lag = in.pitchL[sf];
@@ -142,55 +140,13 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
                     subfr = 0;
                     quad_fence();
                 }
-                // re-whitening: silk_LPC_analysis_filter (celt_fir form), the output samples shared out over the quad
+                // re-whitening (silk_nsq_dev.h), the output samples shared out over the quad: every lane takes a contiguous quarter, so
+                // each sample of xq is read once per lane that needs it
                 const int start_idx = ltp_mem - lag - pord - 5 / 2;
-                const i16 *inp = &NSQ.xq[start_idx + sf * L];
                 const int len = ltp_mem - start_idx;
-                {
-                    // every lane of the quad takes a contiguous quarter of the outputs; the pord previous input samples travel in a
-                    // register window, so each sample of xq is read once per lane that needs it. The outputs leave scaled, as
-                    // silk_nsq_del_dec_scale_states scales exactly these lag + 2 values (:651-660: sLTP_Q15[i] = SMULWB(inv_gain_Q31,
-                    // sLTP[i])): the 16-bit buffer in between is never touched; four inputs per load, four results per store
-                    const int chunk = (len - pord + 3) >> 2, i0 = pord + k * chunk, i1 = imin(len, i0 + chunk);
-                    i32 ig_Q31 = s_inverse32_varq(in.Gains_Q16[sf] > 1 ? in.Gains_Q16[sf] : 1, 47);
-                    if (sf == 0) ig_Q31 = shl32(s_smulwb(ig_Q31, in.LTP_scale_Q14), 2);
-                    i32 *outq = &sLTP_Q15[start_idx];
-                    i32 nA[16], w[16];
-#pragma unroll
-                    for (int m = 0; m < 16; m++) {
-                        nA[m] = m < pord ? (i32)(i16)(-A_Q12[m]) : 0;
-                        w[m] = (m < pord && i0 < i1) ? (i32)inp[i0 - 1 - m] : 0;
-                    }
-                    struct __attribute__((packed, aligned(2))) H4 { i16 v[4]; };
-                    struct __attribute__((packed, aligned(4))) W4 { i32 v[4]; };
-                    int ix = i0;
-                    for (; ix + 4 <= i1; ix += 4) {
-                        const H4 xi4 = *reinterpret_cast<const H4 *>(&inp[ix]);
-                        W4 o;
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            i32 sum = 0;
-#pragma unroll
-                            for (int m = 0; m < 16; m++) sum = s_addw(sum, __mul24(nA[m], w[m]));
-                            const i32 xi = (i32)xi4.v[u];
-                            o.v[u] = s_smulwb(ig_Q31, (i32)sat16(xi + pshr32(sum, 12)));
-#pragma unroll
-                            for (int m = 15; m > 0; m--) w[m] = w[m - 1];
-                            w[0] = xi;
-                        }
-                        *reinterpret_cast<W4 *>(&outq[ix]) = o;
-                    }
-                    for (; ix < i1; ix++) {
-                        i32 sum = 0;
-#pragma unroll
-                        for (int m = 0; m < 16; m++) sum = s_addw(sum, __mul24(nA[m], w[m]));
-                        const i32 xi = (i32)inp[ix];
-                        outq[ix] = s_smulwb(ig_Q31, (i32)sat16(xi + pshr32(sum, 12)));
-#pragma unroll
-                        for (int m = 15; m > 0; m--) w[m] = w[m - 1];
-                        w[0] = xi;
-                    }
-                }
+                const int chunk = (len - pord + 3) >> 2, i0 = pord + k * chunk;
+                nsq_rewhiten_scaled(&NSQ.xq[start_idx + sf * L], &sLTP_Q15[start_idx], A_Q12, pord,
+                                    nsq_rewhite_gain_Q31(in.Gains_Q16[sf], sf == 0, in.LTP_scale_Q14), i0, imin(len, i0 + chunk));
                 ltp_idx = ltp_mem;
                 rewhite = 1;
                 quad_fence();
@@ -198,9 +154,8 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
         }
         // ---- silk_nsq_del_dec_scale_states (NSQ_del_dec.c:632-724) ----
         const i32 gain = in.Gains_Q16[sf];
-        const i32 inv_gain_Q31 = s_inverse32_varq(gain > 1 ? gain : 1, 47);
-        const i32 adj = gain != prev_gain_Q16 ? s_div32_varq(prev_gain_Q16, gain, 16) : (i32)1 << 16;
-        const i32 inv_gain_Q23 = s_rshift_round(inv_gain_Q31, 8);
+        const NsqGains g = nsq_subfr_gains(gain, prev_gain_Q16);
+        const i32 adj = g.gain_adj_Q16, inv_gain_Q23 = g.inv_gain_Q23;
         prev_gain_Q16 = gain;
         {
             const int lg = in.pitchL[sf];
@@ -208,7 +163,6 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
             if (adj != (i32)1 << 16) {
                 {
                     // every lane of the quad takes four consecutive values per access (16 bytes; the record is 4-byte aligned)
-                    struct __attribute__((packed, aligned(4))) Q4 { i32 v[4]; };
                     const int i0 = shp_idx - ltp_mem, body = ltp_mem & ~15;
                     int i = i0 + 4 * k;
                     for (; i + 48 < i0 + body; i += 64) {               // four accesses in flight before the first store
@@ -264,7 +218,13 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
         // the filter coefficients of the subframe in registers (zero beyond the order: a zero tap adds nothing)
         i32 cA[16], cAR[16], cB[5];
 #pragma unroll
-        for (int j = 0; j < 16; j++) { cA[j] = j < pord ? (i32)A_Q12[j] : 0; cAR[j] = j < sord ? (i32)AR_Q13[j] : 0; }
+        for (int j = 0; j < 16; j++) {
+            // both rows have 16 entries whatever the orders: loaded unconditionally (all in flight together), then masked. Written as
+            // guarded loads they are 32 branches, and the compiler is free to wait for each load inside its branch.
+            const i32 a = A_Q12[j], b = AR_Q13[j];
+            cA[j] = j < pord ? a : 0;
+            cAR[j] = j < sord ? b : 0;
+        }
 #pragma unroll
         for (int j = 0; j < 5; j++) cB[j] = B_Q14[j];
         const i32 cAR_last = AR_Q13[sord - 1];
@@ -339,33 +299,8 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
             i32 r_Q10 = s_subw(x_sc_Q10, tmp1);
             if (seed < 0) r_Q10 = (i32)(0u - (u32)r_Q10);
             r_Q10 = s_limit(r_Q10, -(31 << 10), 30 << 10);
-            i32 q1_Q10 = r_Q10 - offset_Q10, q2_Q10, rd1, rd2;
-            const i32 q1_Q0 = q1_Q10 >> 10;
-            if (q1_Q0 > 0) {
-                q1_Q10 = shl32(q1_Q0, 10) - 80 + offset_Q10;
-                q2_Q10 = q1_Q10 + 1024;
-                rd1 = s_smulbb(q1_Q10, Lambda_Q10);
-                rd2 = s_smulbb(q2_Q10, Lambda_Q10);
-            } else if (q1_Q0 == 0) {
-                q1_Q10 = offset_Q10;
-                q2_Q10 = q1_Q10 + (1024 - 80);
-                rd1 = s_smulbb(q1_Q10, Lambda_Q10);
-                rd2 = s_smulbb(q2_Q10, Lambda_Q10);
-            } else if (q1_Q0 == -1) {
-                q2_Q10 = offset_Q10;
-                q1_Q10 = q2_Q10 - (1024 - 80);
-                rd1 = s_smulbb(-q1_Q10, Lambda_Q10);
-                rd2 = s_smulbb(q2_Q10, Lambda_Q10);
-            } else {
-                q1_Q10 = shl32(q1_Q0, 10) + 80 + offset_Q10;
-                q2_Q10 = q1_Q10 + 1024;
-                rd1 = s_smulbb(-q1_Q10, Lambda_Q10);
-                rd2 = s_smulbb(-q2_Q10, Lambda_Q10);
-            }
-            i32 rr = r_Q10 - q1_Q10;
-            rd1 = s_addw(rd1, s_smulbb(rr, rr)) >> 10;
-            rr = r_Q10 - q2_Q10;
-            rd2 = s_addw(rd2, s_smulbb(rr, rr)) >> 10;
+            const NsqLevels lv = nsq_levels(r_Q10, offset_Q10, Lambda_Q10);
+            const i32 q1_Q10 = lv.q1_Q10, q2_Q10 = lv.q2_Q10, rd1 = lv.rd1_Q20 >> 10, rd2 = lv.rd2_Q20 >> 10;
             Cand c0, c1;
             const bool q1_first = rd1 < rd2;
             c0.rd = s_addw(rd, q1_first ? rd1 : rd2);
@@ -494,23 +429,22 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
         // record is only 4-byte aligned, hence the 4-byte-aligned vector type); a forward copy only overwrites what
         // earlier iterations have already read (the source runs frame_length >= 32 elements ahead)
         if ((ltp_mem & 7) == 0 && (frame_length & 7) == 0) {
-            struct __attribute__((packed, aligned(4))) V16 { i32 x, y, z, w; };
-            V16 *dq = reinterpret_cast<V16 *>(NSQ.xq);
-            const V16 *sq = reinterpret_cast<const V16 *>(NSQ.xq + frame_length);
+            Q4 *dq = reinterpret_cast<Q4 *>(NSQ.xq);
+            const Q4 *sq = reinterpret_cast<const Q4 *>(NSQ.xq + frame_length);
             // four pieces per lane are loaded before the first is stored: a stored piece lies below everything a later batch loads
-            auto move_run = [&](V16 *d, const V16 *sc, const int n) {
+            auto move_run = [&](Q4 *d, const Q4 *sc, const int n) {
                 int c = k;
                 for (; c + 12 < n; c += 16) {
-                    V16 v[4];
+                    Q4 v[4];
 #pragma unroll
                     for (int j = 0; j < 4; j++) v[j] = sc[c + 4 * j];
 #pragma unroll
                     for (int j = 0; j < 4; j++) d[c + 4 * j] = v[j];
                 }
-                for (; c < n; c += 4) { const V16 v = sc[c]; d[c] = v; }
+                for (; c < n; c += 4) { const Q4 v = sc[c]; d[c] = v; }
             };
             move_run(dq, sq, ltp_mem / 8);
-            move_run(reinterpret_cast<V16 *>(NSQ.sLTP_shp_Q14), reinterpret_cast<const V16 *>(NSQ.sLTP_shp_Q14 + frame_length), ltp_mem / 4);
+            move_run(reinterpret_cast<Q4 *>(NSQ.sLTP_shp_Q14), reinterpret_cast<const Q4 *>(NSQ.sLTP_shp_Q14 + frame_length), ltp_mem / 4);
         } else {
             for (int m = k; m < ltp_mem; m += 4) {
                 const i16 a = NSQ.xq[m + frame_length];
@@ -526,7 +460,7 @@ __global__ __launch_bounds__(64) void silk_nsq_del_dec_kernel(const opusgpu_nsq_
 
 using namespace ca;
 
-extern "C" size_t opusgpu_silk_nsq_del_dec_workspace_bytes(int n) { return n <= 0 ? 0 : (size_t)n * sizeof(dd::Scratch); }
+extern "C" size_t opusgpu_silk_nsq_del_dec_workspace_bytes(int n) { return n <= 0 ? 0 : (size_t)n * sizeof(NsqScratch); }
 
 extern "C" int opusgpu_silk_nsq_del_dec_batch(const opusgpu_nsq_dd_in *d_in, opusgpu_nsq_state *d_state, opusgpu_nsq_dd_out *d_out, int n,
                                               void *d_workspace, size_t workspace_bytes, void *stream)
@@ -534,11 +468,11 @@ extern "C" int opusgpu_silk_nsq_del_dec_batch(const opusgpu_nsq_dd_in *d_in, opu
     if (n < 0) return OPUSGPU_BAD_ARG;
     if (n == 0) return OPUSGPU_OK;
     if (!d_in || !d_state || !d_out || !d_workspace) return OPUSGPU_BAD_ARG;
-    if (workspace_bytes < (size_t)n * sizeof(dd::Scratch)) return OPUSGPU_BUFFER_TOO_SMALL;
+    if (workspace_bytes < (size_t)n * sizeof(NsqScratch)) return OPUSGPU_BUFFER_TOO_SMALL;
     int *bad = opusgpu_bad_record_counter();
     if (!bad) return OPUSGPU_ALLOC_FAIL;
     hipLaunchKernelGGL(silk_nsq_del_dec_kernel, dim3((n + 15) / 16), dim3(64), 0, (hipStream_t)stream, d_in, d_state, d_out,
-                       (dd::Scratch *)d_workspace, n, bad, (const int *)nullptr);
+                       (NsqScratch *)d_workspace, n, bad, (const int *)nullptr);
     return opusgpu_check_launch();
 }
 
@@ -549,7 +483,7 @@ extern "C" int opusgpu_silk_nsq_del_dec_rows(const opusgpu_nsq_dd_in *d_in, opus
     if (m <= 0) return m < 0 ? OPUSGPU_BAD_ARG : OPUSGPU_OK;
     int *bad = opusgpu_bad_record_counter();
     if (!bad) return OPUSGPU_ALLOC_FAIL;
-    hipLaunchKernelGGL(silk_nsq_del_dec_kernel, dim3((m + 15) / 16), dim3(64), 0, stream, d_in, d_state, d_out, (dd::Scratch *)d_workspace, m, bad,
+    hipLaunchKernelGGL(silk_nsq_del_dec_kernel, dim3((m + 15) / 16), dim3(64), 0, stream, d_in, d_state, d_out, (NsqScratch *)d_workspace, m, bad,
                        d_rows);
     return opusgpu_check_launch();
 }

@@ -401,6 +401,26 @@ extern "C" void emu_silk_rate_control(opusgpu_silk_rate_ctl *ctl, const int32_t 
     for (long r = 0; r < n; r++) ca::silk_rate_control_step_dev(ctl[r], nBits[r]);
 }
 
+// ---- silk_NSQ, host build of concentus_amd/csrc/silk_nsq_dev.h (tests/test_silk_nsq_cpu.py): the kernel's gate and its one call.
+// silk_validate.h is written with the device qualifiers only; for this include they mean nothing.
+#define __device__
+#define __forceinline__ inline
+#include "../../concentus_amd/csrc/silk_validate.h"
+#undef __device__
+#undef __forceinline__
+#include "../../concentus_amd/csrc/silk_nsq_dev.h"
+extern "C" void emu_silk_nsq(const opusgpu_nsq_in *in, opusgpu_nsq_state *st, opusgpu_nsq_out *out, long n)
+{
+    static ca::NsqScratch ws;
+    for (long r = 0; r < n; r++) {
+        if (!ca::nsq_record_ok(in[r], st[r].lagPrev)) {          // state untouched, no pulses
+            memset(out[r].pulses, 0, sizeof(out[r].pulses));
+            continue;
+        }
+        ca::silk_nsq_record_dev(in[r], st[r], out[r].pulses, ws.sLTP_Q15);
+    }
+}
+
 // ---- range coder scripts (csrc/ec_script.h) on the host build: the same device code the hooks opusgpu_ec_enc_script /
 // opusgpu_ec_dec_script run, for the CPU tier (tests/test_ec_script_cpu.py). ec = the 11 fields in the order of refcap's ec_pack:
 // storage end_offs end_window nend_bits nbits_total offs rng val ext rem error.

@@ -7,6 +7,8 @@ celt/entcode.h:63-94 (x86-64 SysV ABI). Nothing here is imported by the product 
 import ctypes as C
 import os
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_PATH = os.path.join(ROOT, "oracle", "_ref", "libopus_ref.so")
 
@@ -139,3 +141,36 @@ def static_table(name, fmt, count):
         f.seek(off)
         raw = f.read(size)
     return list(struct.unpack("<%d%s" % (count, fmt), raw))
+
+
+# ---- silk_NSQ_c / silk_NSQ_del_dec_c with the reference's own argument list (tests/test_hooks_gpu.py, tests/test_silk_nsq_cpu.py) ----
+def nsq_ref_structs(rec_in, dd):
+    """The reference's silk_encoder_state / SideInfoIndices (zeroed, only the fields the quantisers read are set, at the
+    offsets of include/opusgpu_hooks.h) from one function-boundary record."""
+    from test_hooks_layout import header_defines
+    d = header_defines()
+    hdr = rec_in[:48].view(np.int32)          # nb_subfr, subfr_length, frame_length, ltp_mem_length, predictLPCOrder, shapingLPCOrder, signalType, quantOffsetType, NLSFInterpCoef_Q2, Seed, Lambda_Q10, LTP_scale_Q14
+    enc = np.zeros(d["OPUSGPU_REF_SIZEOF_SILK_ENCODER_STATE"], np.uint8)
+    for off, v in ((d["OPUSGPU_REF_OFF_NB_SUBFR"], hdr[0]), (d["OPUSGPU_REF_OFF_SUBFR_LENGTH"], hdr[1]),
+                   (d["OPUSGPU_REF_OFF_FRAME_LENGTH"], hdr[2]), (d["OPUSGPU_REF_OFF_LTP_MEM_LENGTH"], hdr[3]),
+                   (d["OPUSGPU_REF_OFF_PREDICT_LPC_ORDER"], hdr[4]), (d["OPUSGPU_REF_OFF_SHAPING_LPC_ORDER"], hdr[5])):
+        enc[off:off + 4].view(np.int32)[0] = v
+    if dd is not None:
+        enc[d["OPUSGPU_REF_OFF_N_STATES_DEL_DEC"]:][:4].view(np.int32)[0] = dd[0]
+        enc[d["OPUSGPU_REF_OFF_WARPING_Q16"]:][:4].view(np.int32)[0] = dd[1]
+    idx = np.zeros(d["OPUSGPU_REF_SIZEOF_SIDE_INFO_INDICES"], np.int8)
+    idx[d["OPUSGPU_REF_OFF_SIGNAL_TYPE"]] = hdr[6]
+    idx[d["OPUSGPU_REF_OFF_QUANT_OFFSET_TYPE"]] = hdr[7]
+    idx[d["OPUSGPU_REF_OFF_NLSF_INTERP_COEF_Q2"]] = hdr[8]
+    idx[d["OPUSGPU_REF_OFF_SEED"]] = hdr[9]
+    return enc, idx, int(hdr[10]), int(hdr[11])
+
+
+def nsq_arrays(rec_in):
+    """The array arguments of silk_NSQ / silk_NSQ_del_dec from one function-boundary record: x_Q3, PredCoef_Q12, LTPCoef_Q14, AR2_Q13,
+    HarmShapeGain_Q14, Tilt_Q14, LF_shp_Q14, Gains_Q16, pitchL."""
+    i32 = lambda lo, n: np.ascontiguousarray(rec_in[lo:lo + 4 * n].view(np.int32))
+    harm, tilt, lf, gains, pitch = (i32(48 + 16 * k, 4) for k in range(5))
+    x_Q3 = i32(128, 320)
+    i16 = lambda lo, n: np.ascontiguousarray(rec_in[lo:lo + 2 * n].view(np.int16))
+    return x_Q3, i16(1408, 32), i16(1472, 20), i16(1512, 64), harm, tilt, lf, gains, pitch

@@ -105,35 +105,6 @@ def test_renormalise_vector(L, ref):
             assert np.array_equal(a, b), (n, amp, gain)
 
 
-def _ref_structs(rec_in, dd):
-    """The reference's silk_encoder_state / SideInfoIndices (zeroed, only the fields the quantisers read are set, at the
-    offsets of include/opusgpu_hooks.h) from one function-boundary record."""
-    d = header_defines()
-    hdr = rec_in[:48].view(np.int32)          # nb_subfr, subfr_length, frame_length, ltp_mem_length, predictLPCOrder, shapingLPCOrder, signalType, quantOffsetType, NLSFInterpCoef_Q2, Seed, Lambda_Q10, LTP_scale_Q14
-    enc = np.zeros(d["OPUSGPU_REF_SIZEOF_SILK_ENCODER_STATE"], np.uint8)
-    for off, v in ((d["OPUSGPU_REF_OFF_NB_SUBFR"], hdr[0]), (d["OPUSGPU_REF_OFF_SUBFR_LENGTH"], hdr[1]),
-                   (d["OPUSGPU_REF_OFF_FRAME_LENGTH"], hdr[2]), (d["OPUSGPU_REF_OFF_LTP_MEM_LENGTH"], hdr[3]),
-                   (d["OPUSGPU_REF_OFF_PREDICT_LPC_ORDER"], hdr[4]), (d["OPUSGPU_REF_OFF_SHAPING_LPC_ORDER"], hdr[5])):
-        enc[off:off + 4].view(np.int32)[0] = v
-    if dd is not None:
-        enc[d["OPUSGPU_REF_OFF_N_STATES_DEL_DEC"]:][:4].view(np.int32)[0] = dd[0]
-        enc[d["OPUSGPU_REF_OFF_WARPING_Q16"]:][:4].view(np.int32)[0] = dd[1]
-    idx = np.zeros(d["OPUSGPU_REF_SIZEOF_SIDE_INFO_INDICES"], np.int8)
-    idx[d["OPUSGPU_REF_OFF_SIGNAL_TYPE"]] = hdr[6]
-    idx[d["OPUSGPU_REF_OFF_QUANT_OFFSET_TYPE"]] = hdr[7]
-    idx[d["OPUSGPU_REF_OFF_NLSF_INTERP_COEF_Q2"]] = hdr[8]
-    idx[d["OPUSGPU_REF_OFF_SEED"]] = hdr[9]
-    return enc, idx, int(hdr[10]), int(hdr[11])
-
-
-def _arrays(rec_in):
-    i32 = lambda lo, n: np.ascontiguousarray(rec_in[lo:lo + 4 * n].view(np.int32))
-    harm, tilt, lf, gains, pitch = (i32(48 + 16 * k, 4) for k in range(5))
-    x_Q3 = i32(128, 320)
-    i16 = lambda lo, n: np.ascontiguousarray(rec_in[lo:lo + 2 * n].view(np.int16))
-    return x_Q3, i16(1408, 32), i16(1472, 20), i16(1512, 64), harm, tilt, lf, gains, pitch
-
-
 @pytest.mark.parametrize("which", ["nsq", "del_dec"])
 def test_silk_nsq_hooks_with_the_reference_argument_list(L, ref, which):
     r, _ = ref
@@ -146,10 +117,10 @@ def test_silk_nsq_hooks_with_the_reference_argument_list(L, ref, which):
     for k in range(0, rin.shape[0], 5):
         rec = np.ascontiguousarray(rin[k])
         dd = None if which == "nsq" else rec[1640:1648].view(np.int32)
-        x_Q3, pred, ltp, ar2, harm, tilt, lf, gains, pitch = _arrays(rec)
+        x_Q3, pred, ltp, ar2, harm, tilt, lf, gains, pitch = reflib.nsq_arrays(rec)
         out = []
         for fn in (fn_ref, fn_gpu):
-            enc, idx, lam, ltps = _ref_structs(rec, dd)
+            enc, idx, lam, ltps = reflib.nsq_ref_structs(rec, dd)
             st = np.ascontiguousarray(st_in[k]).copy()
             pulses = np.zeros(320, np.int8)
             fn(p(enc), p(st), p(idx), p(x_Q3), p(pulses), p(pred), p(ltp), p(ar2), p(harm), p(tilt), p(lf), p(gains), p(pitch),

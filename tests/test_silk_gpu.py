@@ -74,6 +74,30 @@ def test_silk_kernels_full_size_vs_oracle(ca):
     assert np.array_equal(st[idx], sst)
 
 
+def test_nsq_short_lags_and_ragged_subframes_vs_oracle(ca):
+    """The paths of silk_nsq_kernel that no captured record reaches (tests/nsq_cases.py: voiced lags 3-7 and 8-11, subframes of 78 / 79
+    samples, unvoiced frames after a lag of 5 or 0) next to the captured records, 140 records = a partial last wavefront: pulses
+    and every byte of silk_nsq_state against the CPU oracle (pinned on the reference for these records by tests/test_silk_nsq_cpu.py)."""
+    import torch
+    import nsq_cases
+    ni, st0, cls = nsq_cases.nsq_short_lag_corpus()
+    nsq_cases.check_nsq_corpus_reaches_every_path(ni, st0, cls)
+    assert ni.shape[0] % 64 != 0
+    ca.silk.bad_records()
+    st = _dev(st0)
+    pulses = ca.silk_NSQ(_dev(ni), st)
+    torch.cuda.synchronize()
+    assert ca.silk.bad_records() == 0
+    pulses, st = pulses.cpu().numpy().view(np.uint8), st.cpu().numpy()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    want_st = st0.copy(); want = np.zeros((ni.shape[0], 320), np.uint8)
+    oraclelib.lib().orc_silk_nsq_batch(p(ni), p(want_st), p(want), ni.shape[0])
+    bad = np.nonzero((pulses != want).any(1))[0]
+    assert bad.size == 0, ("pulses differ", bad[:8], [nsq_cases.CLASSES[c] for c in cls[bad[:8]]])
+    bad = np.nonzero((st != want_st).any(1))[0]
+    assert bad.size == 0, ("NSQ state differs", bad[:8], [nsq_cases.CLASSES[c] for c in cls[bad[:8]]])
+
+
 def test_silk_kernels_match_fresh_capture_if_present(ca):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if not os.path.exists(os.path.join(root, "oracle", "_ref", "libopus_ref_silkcap.so")):
@@ -146,6 +170,25 @@ def test_del_dec_full_size_vs_oracle(ca):
     orc.orc_silk_nsq_del_dec_batch(p(sdi), p(sst), p(sdo), idx.size)
     assert np.array_equal(out[idx], sdo), np.nonzero((out[idx] != sdo).any(1))[0][:8]
     assert np.array_equal(st[idx], sst), np.nonzero((st[idx] != sst).any(1))[0][:8]
+
+
+def test_del_dec_short_decision_delays_vs_oracle(ca):
+    """The 84 captured records with the voiced lags overwritten to 4 .. 11 (tests/nsq_cases.py), so that the decision delay is
+    lag - 3 = 1 .. 8 instead of the 32 of every captured record; 133 records = a ragged last workgroup."""
+    import torch
+    import nsq_cases
+    di, st0 = nsq_cases.dd_short_delay_corpus(133)
+    ca.silk.bad_records()
+    st = _dev(st0)
+    out = ca.silk_NSQ_del_dec(_dev(di), st)
+    torch.cuda.synchronize()
+    assert ca.silk.bad_records() == 0
+    out, st = out.cpu().numpy(), st.cpu().numpy()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    want_st = st0.copy(); want = np.zeros((di.shape[0], 324), np.uint8)
+    oraclelib.lib().orc_silk_nsq_del_dec_batch(p(di), p(want_st), p(want), di.shape[0])
+    assert np.array_equal(out, want), np.nonzero((out != want).any(1))[0][:8]
+    assert np.array_equal(st, want_st), np.nonzero((st != want_st).any(1))[0][:8]
 
 
 def test_del_dec_matches_fresh_capture_if_present(ca):
