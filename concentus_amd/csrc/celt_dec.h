@@ -1294,12 +1294,13 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
 {
     DecResult res;
     res.samples = OPUSGPU_INVALID_PACKET;
-    res.final_range = 0;
+    res.final_range = st->final_range;                  // a rejected packet leaves OPUS_GET_FINAL_RANGE as it was (src/opus_decoder.c:636-639)
     st->mid_valid = 0;
     F.X = (x16_t *)st->mid_X;
     F.norm = (x16_t *)st->mid_norm;
     const int N = FRAME, LM = LM3, M = M8;
-    if (len < 2) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }   // len == 1: DTX, the PLC entry point's business
+    // len == 1 or 2: a payload of no or one byte is DTX (src/opus_decoder.c:245-251), the PLC entry point's business
+    if (len < 3) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }
     const int toc = data[0];
     if (!celt_toc_accepted(toc)) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
     data++;
@@ -1323,6 +1324,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     else if (tell == 1) silence = ec_dec_bit_logp(dec, 15);
     else silence = 0;
     if (silence) {
+        if (len > 2) CA_COUNT("corrupt_silence_long", 1);
         tell = len * 8;
         dec.nbits_total += tell - ec_tell(dec);
     }
@@ -1331,6 +1333,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     if (tell + 16 <= total_bits) {
         if (ec_dec_bit_logp(dec, 1)) {
             int octave = (int)ec_dec_uint(dec, 6);
+            if (octave == 5) CA_COUNT("corrupt_pf_octave5", 1);
             postfilter_pitch = (16 << octave) + (int)ec_dec_bits(dec, (u32)(4 + octave)) - 1;
             int qg = (int)ec_dec_bits(dec, 3);
             if (ec_tell(dec) + 2 <= total_bits) postfilter_tapset = ec_dec_icdf(dec, CLT_tapset_icdf, 2);
@@ -1344,6 +1347,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
         tell = ec_tell(dec);
     }
     const int shortBlocks = isTransient ? M : 0;
+    if (tell + 3 > total_bits) CA_COUNT("corrupt_intra_skipped", 1);
     const int intra_ener = tell + 3 <= total_bits ? ec_dec_bit_logp(dec, 3) : 0;
     CA_STAMP_F(F, 0);
     unquant_coarse_energy_dec(oldBandE, intra_ener, dec, C, end);
@@ -1352,6 +1356,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     tell = ec_tell(dec);
     int spread_decision = SPREAD_NORMAL;
     if (tell + 4 <= total_bits) spread_decision = ec_dec_icdf(dec, CLT_spread_icdf, 5);
+    else CA_COUNT("corrupt_spread_skipped", 1);
     for (int i = 0; i < NB; i++) {                                                              // init_caps (celt.c:255)
         int Nb = (CLT_eband5ms[i + 1] - CLT_eband5ms[i]) << LM;
         F.cap[i] = ((CLT_cache_caps50[NB * (2 * LM + C - 1) + i] + 64) * C * Nb) >> 2;
@@ -1374,6 +1379,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
         F.offsets[i] = boost;
         if (boost > 0) dynalloc_logp = imax(2, dynalloc_logp - 1);
     }
+    if (tell + (6 << BITRES) > total_bits) CA_COUNT("corrupt_trim_default", 1);
     const int alloc_trim = tell + (6 << BITRES) <= total_bits ? ec_dec_icdf(dec, CLT_trim_icdf, 7) : 5;
     i32 bits = ((len * 8) << BITRES) - (i32)ec_tell_frac(dec) - 1;
     const int anti_collapse_rsv = isTransient && LM >= 2 && bits >= ((LM + 2) << BITRES) ? (1 << BITRES) : 0;
@@ -1391,6 +1397,7 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     if (anti_collapse_rsv > 0) anti_collapse_on = (int)ec_dec_bits(dec, 1);
     unquant_energy_finalise_dec(oldBandE, F.fine_quant, F.fine_priority, len * 8 - ec_tell(dec), dec, C, end);
     if (anti_collapse_on) {
+        CA_COUNT("corrupt_anti_collapse", 1);
         if (C == 1) CA_COUNT("chbw_mono_anti_collapse", 1);
         anti_collapse_dec(F, oldBandE, oldLogE, oldLogE2, st->rng, C, end);
     }
@@ -1436,10 +1443,10 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     st->loss_count = 0;
     st->started = 1;                                                                             // the Opus layer's prev_mode (src/opus_decoder.c:584)
     CA_STAMP_F(F, 11);
-    if (ec_tell(dec) > 8 * len) { res.samples = OPUSGPU_INTERNAL_ERROR; return res; }
-    if (dec.error) st->error = 1;
+    if (ec_tell(dec) > 8 * len) { CA_COUNT("corrupt_tell_past_end", 1); res.samples = OPUSGPU_INTERNAL_ERROR; return res; }
+    if (dec.error) { CA_COUNT("corrupt_dec_error", 1); st->error = 1; }
     res.samples = N;
-    res.final_range = dec.rng;
+    res.final_range = st->final_range = dec.rng;
     return res;
 }
 

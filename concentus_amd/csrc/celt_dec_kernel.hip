@@ -20,7 +20,7 @@ namespace ca {
 
 // A = streams per wavefront (64, or 32 / 16 with 2 / 4 partly filled waves per 64-stream workgroup; see
 // celt_back_lane_kernel.hip)
-// PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is a one-byte DTX packet is left to
+// PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is a DTX packet (one or two bytes) is left to
 // the concealment kernels (celt_dec_plc_kernel.hip), which find it by st->mid_plc
 template <int A, bool PLC>
 __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu_celt_dec_state *states, const u8 *__restrict__ packets,
@@ -38,13 +38,14 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
     F.lds_pvq16 = (CA_AS_LDS i16 *)(g_lds_pvq16 + slot);
     const int ln = PLC && !len ? 0 : len[k];
     if (PLC) {
-        const int toc = ln == 1 && packet_stride >= 1 ? packets[(size_t)k * packet_stride] : -1;
-        const bool dtx = toc >= 0 && celt_toc_accepted(toc);
+        const int toc = (ln == 1 || ln == 2) && packet_stride >= 1 ? packets[(size_t)k * packet_stride] : -1;
+        const bool dtx = toc >= 0 && celt_plc_is_dtx(toc, ln);
         const bool lost = ln == 0 || dtx;
         states[k].mid_plc = lost ? OPUSGPU_PLC_LOST : OPUSGPU_PLC_NONE;
         if (lost) {
             if (dtx) celt_plc_dtx_toc(states + k, toc);
             states[k].mid_valid = 0;
+            states[k].final_range = 0;
             ret[k] = FRAME;
             rng[k] = 0;
             return;
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
         // a length past this stream's row would read the next stream's packet (or, for the last stream, past the slab)
         states[k].mid_valid = 0;
         ret[k] = OPUSGPU_BAD_ARG;
-        rng[k] = 0;
+        rng[k] = states[k].final_range;
         return;
     }
     // The streams of a wavefront may differ in channel count and bandwidth, so both are run-time values of the lane -- unless

@@ -529,10 +529,12 @@ CA_DEV void celt_deemphasis_channel(opusgpu_celt_dec_state *st, int c, i16 *pcm)
     st->preemph_memD[c] = m;
 }
 
-// which packets opusgpu_decode_batch_plc conceals: a lost one (no length) and DTX, a packet that is nothing but the TOC byte
-// (src/opus_decoder.c:246-251); only the TOCs this decoder implements. The stream takes such a TOC's bandwidth and channel
+// which packets opusgpu_decode_batch_plc conceals: a lost one (no length) and DTX, a packet whose payload behind the TOC byte is
+// empty or a single byte (src/opus_decoder.c:245-251: "Payloads of 1 (2 including ToC) or 0 trigger the PLC/DTX"); only the
+// TOCs this decoder implements. The stream takes such a TOC's bandwidth and channel
 // count before it is concealed (celt_plc_dtx_toc).
 CA_DEV bool celt_plc_conceals(const u8 *data, int len);
+CA_DEV bool celt_plc_is_dtx(int toc, int len) { return (len == 1 || len == 2) && celt_toc_accepted(toc); }
 
 CA_DEV void celt_plc_dtx_toc(opusgpu_celt_dec_state *st, int toc)
 {
@@ -548,7 +550,8 @@ static int g_emu_dtx_toc = -1;
 
 CA_DEV bool celt_plc_conceals(const u8 *data, int len)
 {
-    const bool dtx = len == 1 && celt_toc_accepted(data[0]);
+    const bool dtx = (len == 1 || len == 2) && celt_plc_is_dtx(data[0], len);
+    if (dtx && len == 2) CA_COUNT("corrupt_payload_one_byte", 1);
 #if defined(CA_HOST_EMU)
     g_emu_dtx_toc = dtx ? data[0] : -1;
 #endif
@@ -579,7 +582,7 @@ CA_DEV DecResult celt_decode_lost_frame(LP_ &P, S &L, opusgpu_celt_dec_state *st
     }
     DecResult r;
     r.samples = FRAME;
-    r.final_range = 0;
+    r.final_range = st->final_range = 0;                                           // src/opus_decoder.c:579-580
     return r;
 }
 

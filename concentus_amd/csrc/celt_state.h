@@ -76,7 +76,7 @@ typedef struct opusgpu_celt_dec_state {
     int32_t last_pitch_index;
     int32_t started;
     int32_t last_end, last_channels;
-    int32_t reserved[1];
+    uint32_t final_range;                                  /* OPUS_GET_FINAL_RANGE: the last accepted packet's, 0 after a concealed frame */
     int16_t oldBandE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE[2 * OPUSGPU_CELT_NBANDS];
     int16_t oldLogE2[2 * OPUSGPU_CELT_NBANDS];
@@ -111,7 +111,7 @@ typedef struct opusgpu_celt_dec_state {
 static_assert(offsetof(opusgpu_celt_dec_state, decode_mem) % 16 == 0, "decode_mem must stay 16-byte aligned");
 static_assert(sizeof(opusgpu_celt_dec_state) % 16 == 0, "sizeof(opusgpu_celt_dec_state) must stay a multiple of 16");
 static_assert(offsetof(opusgpu_celt_dec_state, last_end) == 52 && offsetof(opusgpu_celt_dec_state, oldBandE) == 64,
-              "last_end / last_channels took two of the reserved words: no offset may move");
+              "last_end / last_channels / final_range took the reserved words: no offset may move");
 #endif
 
 #ifdef __cplusplus

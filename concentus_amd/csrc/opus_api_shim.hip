@@ -281,7 +281,9 @@ extern "C" int opusgpu_decode(OpusGpuDecoder *st, const unsigned char *data, int
     if (hipMemcpyAsync(st->d_pkt, data, (size_t)len, hipMemcpyHostToDevice, st->stream) != hipSuccess ||
         hipMemcpyAsync(st->d_len, &len, 4, hipMemcpyHostToDevice, st->stream) != hipSuccess)
         return OPUSGPU_INTERNAL_ERROR;
-    int rc = opusgpu_decode_batch(st->d_state, st->d_pkt, 1280, st->d_len, st->d_pcm, st->d_ret, st->d_rng, 1, st->stream);
+    // a payload of no or one byte behind the TOC is DTX: concealed (src/opus_decoder.c:245-251)
+    int rc = len <= 2 ? opusgpu_decode_batch_plc(st->d_state, st->d_pkt, 1280, st->d_len, st->d_pcm, st->d_ret, st->d_rng, 1, st->stream)
+                      : opusgpu_decode_batch(st->d_state, st->d_pkt, 1280, st->d_len, st->d_pcm, st->d_ret, st->d_rng, 1, st->stream);
     if (rc < 0) return rc;
     if (hipMemcpyAsync(&ret, st->d_ret, 4, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||
         hipMemcpyAsync(&st->final_range, st->d_rng, 4, hipMemcpyDeviceToHost, st->stream) != hipSuccess ||

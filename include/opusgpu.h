@@ -163,7 +163,7 @@ int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_states, const i
  *
  * decoded as opus_decode() does on a decoder made with opus_decoder_create(48000, 2): a mono packet comes out on both
  * channels, and the streams of one call may differ in TOC and change it from packet to packet. Every other TOC (SILK,
- * hybrid, codes 1-3, other frame sizes) gives that stream OPUSGPU_UNIMPLEMENTED, as does a one-byte packet here. One
+ * hybrid, codes 1-3, other frame sizes) gives that stream OPUSGPU_UNIMPLEMENTED, as does a packet of one or two bytes here. One
  * call decodes the next packet of every stream:
  *   d_states   device, n x opusgpu_celt_dec_state_size() bytes, initialised once with
  *              opusgpu_celt_dec_state_init (== opus_decoder_create(48000, 2)); advanced by one frame per call.
@@ -171,8 +171,10 @@ int opusgpu_encode_batch(const opusgpu_celt_config *cfg, void *d_states, const i
  *   d_pcm      device, int16 [n][960][2] interleaved (as opus_decode's pcm with frame_size 960), 16-byte aligned
  *              (it is written 16 bytes at a time; OPUSGPU_BAD_ARG otherwise).
  *   d_ret      device, int32 [n]: 960, or a negative OPUSGPU_* code for that stream (opus_decode's return value):
- *              OPUSGPU_UNIMPLEMENTED for other TOCs and for 1-byte packets (loss concealment / DTX).
- *   d_rng      device, uint32 [n]: OPUS_GET_FINAL_RANGE after the packet (equals the encoder's).
+ *              OPUSGPU_UNIMPLEMENTED for other TOCs and for packets of 1 or 2 bytes (loss concealment / DTX),
+ *              OPUSGPU_INVALID_PACKET for more than 1276 bytes, OPUSGPU_BAD_ARG for a length past packet_stride.
+ *   d_rng      device, uint32 [n]: OPUS_GET_FINAL_RANGE after the packet (equals the encoder's); a rejected packet
+ *              leaves the stream's state alone and reports the final range the stream had before it.
  * Asynchronous on hip_stream. */
 int opusgpu_celt_dec_state_size(void);
 int opusgpu_celt_dec_state_init(void *d_states, int n_streams, void *hip_stream);
@@ -181,7 +183,7 @@ int opusgpu_decode_batch(void *d_states, const unsigned char *d_packets, int pac
 /* The same call with packet loss concealment (celt_decode_lost, celt/celt_decoder.c:395-711, bit-exact): the arguments of
  * opusgpu_decode_batch, and
  *   d_len[i] == 0                  stream i lost its packet: opus_decode(st, NULL, 0, pcm, 960, 0);
- *   d_len[i] == 1, TOC as above    DTX, concealed in the same way (src/opus_decoder.c:246-251) after the stream has taken the
+ *   d_len[i] == 1 or 2, TOC as above  DTX (a payload of no or one byte), concealed in the same way (src/opus_decoder.c:246-251) after the stream has taken the
  *                                  TOC's bandwidth and channel count (:683-686); other one-byte packets
  *                                  return OPUSGPU_UNIMPLEMENTED;
  *   d_len == NULL                  every stream is lost; d_packets may then be NULL.

@@ -16,6 +16,12 @@ extern "C" long emu_plc_count(const char *name)
     auto it = g_counts.find(name);
     return it == g_counts.end() ? 0 : it->second;
 }
+// per-frame view of the counters: after every frame of emu_celt_decode_frames_plc the running totals of the named counters go
+// to out[frame * n + i], so that a test can tell which frame reached a branch (names == NULL switches it off)
+static const char *const *g_trace_names = nullptr;
+static int g_trace_n = 0;
+static long *g_trace_out = nullptr;
+extern "C" void emu_plc_trace_counts(const char *const *names, int n, long *out) { g_trace_names = names; g_trace_n = names ? n : 0; g_trace_out = out; }
 #include "../../concentus_amd/csrc/celt_plc.h"
 
 using namespace ca;
@@ -53,6 +59,7 @@ extern "C" int emu_celt_decode_frames_plc(const unsigned char *packets, int stri
         }
         ret[n] = r.samples;
         rng[n] = r.final_range;
+        for (int i = 0; i < g_trace_n; i++) g_trace_out[(size_t)n * g_trace_n + i] = emu_plc_count(g_trace_names[i]);
     }
     free(F);
     free(L);

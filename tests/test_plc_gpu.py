@@ -1,6 +1,7 @@
 """GPU tests of the packet loss concealment (opusgpu_decode_batch_plc, opusgpu_decode_lost): PCM, return value and final range
 bit-exact against the compiled reference's opus_decode() with lost packets -- committed (tests/golden/plc_golden.npz), live when
-oracle/_ref travelled -- and against the host emulation of the same sources. Only valid packets and the lengths 0 and 1 are fed."""
+oracle/_ref travelled -- and against the host emulation of the same sources. Only valid packets and the lengths 0 and 1 are fed
+here; corrupt and truncated packets, and losses right after them, are in tests/test_decode_corrupt_gpu.py."""
 import ctypes as C
 import os
 import subprocess
