@@ -53,13 +53,16 @@ struct __attribute__((aligned(16))) SynthLds {
 CA_DEV u32 celt_lcg_rand(u32 seed) { return 1664525u * seed + 1013904223u; }                   // bands.c:63
 
 // ---- energies ----------------------------------------------------------------------------------------
-CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C, int end)      // quant_bands.c:434
+// (ANYLM here and below: LM is the run-time argument lm; without it the constant 3, folded before the body is inlined anywhere)
+template <bool ANYLM = false>
+CA_DEV void unquant_coarse_energy_dec(i16 *oldE, int intra, RangeDec &dec, int C, int end, const int lm = LM3)   // quant_bands.c:434
 {
-    const u8 *prob_model = CLT_e_prob_model + (LM3 * 2 + intra) * 42;
+    const int LM = ANYLM ? lm : (int)LM3;
+    const u8 *prob_model = CLT_e_prob_model + (LM * 2 + intra) * 42;
     i32 prev[2] = {0, 0};
     i32 coef, beta;
     if (intra) { coef = 0; beta = 4915; }                                                      // beta_intra
-    else { beta = CLT_beta_coef[LM3]; coef = CLT_pred_coef[LM3]; }
+    else { beta = CLT_beta_coef[LM]; coef = CLT_pred_coef[LM]; }
     const i32 budget = (i32)dec.storage * 8;
     for (int i = 0; i < end; i++) {
         for (int c = 0; c < C; c++) {
@@ -114,9 +117,10 @@ CA_DEV void unquant_energy_finalise_dec(i16 *oldE, const i32 *fine_quant, const 
     }
 }
 
-CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec, int end)                 // celt_decoder.c:352
+template <bool ANYLM = false>
+CA_DEV void tf_decode_dec(int isTransient, i32 *tf_res, RangeDec &dec, int end, const int lm = LM3)   // celt_decoder.c:352
 {
-    const int LM = LM3;
+    const int LM = ANYLM ? lm : (int)LM3;
     u32 budget = dec.storage * 8;
     u32 tell = (u32)ec_tell(dec);
     int logp = isTransient ? 2 : 4;
@@ -939,16 +943,16 @@ CA_DEV void negate_band_dec(x16_t *Y, int N)
     for (int j = 0; j < N; j++) Y[j] = (i16)(-Y[j]);
 }
 
-// quant_all_bands (bands.c:1337-1502), encode = 0, start 0, LM 3; C channels (Y_ == NULL for C == 1: a band is then ONE
+// quant_all_bands (bands.c:1337-1502), encode = 0, start 0; LM 3 unless the caller passes its packet's; C channels (Y_ == NULL for C == 1: a band is then ONE
 // quant_band job, with one collapse mask) over the bands [0, end)
-template <class D>
+template <bool ANYLM = false, class D>
 CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread, int dual_stereo, int intensity,
-                                i32 total_bits, i32 balance, int codedBands, u32 *seed, const int C, const int end)
+                                i32 total_bits, i32 balance, int codedBands, u32 *seed, const int C, const int end, const int lm = LM3)
 {
-    const int LM = LM3, M = M8;
+    const int LM = ANYLM ? lm : (int)LM3, M = ANYLM ? 1 << lm : (int)M8;
     const int B = shortBlocks ? M : 1;
     const i16 *eB = CLT_eband5ms;
-    x16_t *X_ = F.X, *Y_ = F.X + FRAME;
+    x16_t *X_ = F.X, *Y_ = F.X + (ANYLM ? M * (FRAME / M8) : (int)FRAME);      // (the second channel follows the frame's N = 120 M bins)
     x16_t *norm = F.norm, *norm2 = F.norm + M * eB[NB - 1];
     x16_t *lowband_scratch = X_ + M * eB[NB - 1];
     int lowband_offset = 0, update_lowband = 1;
@@ -1108,11 +1112,12 @@ CA_DEV void quant_all_bands_dec(D &F, RangeDec &dec, int shortBlocks, int spread
     *seed = ctx.seed;
 }
 
-// anti_collapse (bands.c:241-335), LM = 3
-template <class D>
-CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const i16 *prev2logE, u32 seed, const int C, const int end)
+// anti_collapse (bands.c:241-335); LM 3 unless the caller passes its packet's (the reference runs it at LM >= 2 only)
+template <bool ANYLM = false, class D>
+CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const i16 *prev2logE, u32 seed, const int C, const int end,
+                              const int lm = LM3)
 {
-    const int LM = LM3;
+    const int LM = ANYLM ? lm : (int)LM3;
     for (int i = 0; i < end; i++) {
         const int N0 = CLT_eband5ms[i + 1] - CLT_eband5ms[i];
         int depth = (int)((u32)(1 + F.pulses[i]) / (u32)N0) >> LM;
@@ -1141,10 +1146,10 @@ CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const
             } else {
                 r = 0;
             }
-            r = (i16)mul16_16_q14(23170, imin(23169, r));                                      // LM == 3
+            if (LM == 3) r = (i16)mul16_16_q14(23170, imin(23169, r));                         // bands.c:302-303: at LM == 3 alone
             r = (i16)(imin(thresh, r) >> 1);
             r = (i16)(mul16_16_q15(sqrt_1, r) >> shift);
-            x16_t *X = F.X + c * FRAME + (CLT_eband5ms[i] << LM);
+            x16_t *X = F.X + c * (ANYLM ? (FRAME / M8) << LM : (int)FRAME) + (CLT_eband5ms[i] << LM);
             int renormalize = 0;
             for (int k = 0; k < 1 << LM; k++) {
                 if (!(F.collapse_masks[i * C + c] & 1 << k)) {
@@ -1164,10 +1169,12 @@ CA_DEV void anti_collapse_dec(D &F, const i16 *logE, const i16 *prev1logE, const
 // that pays 21 dependent steps (the band's energy from HBM, then its 8-176 bins, a sixth of the lanes busy on the narrow bands).
 // Here the 21 gains are computed side by side (one lane per band), and the 960 bins are then walked 64 at a time with all of a
 // lane's loads issued together; a bin finds its band through a 120-entry table (bands start at multiples of eight bins).
-template <class S>
-CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int silence, int end)
+// ANY: M = 1 << LM and N = 120 M of a short frame (bands start at multiples of M bins: the same table, read at j >> LM), walked
+// in a plain lane-strided loop.
+template <bool ANY = false, class S>
+CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int silence, int end, const int LM = LM3)
 {
-    const int N = FRAME;
+    const int N = (FRAME / M8) << LM;
     i32 *freq = L.freq;
     for (int i = lane(); i < NB; i += LANES) {
         i32 lg = add16(bandLogE[i], shl16(CLT_eMeans[i], 6));
@@ -1179,7 +1186,7 @@ CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int s
         L.dn_gain[i] = (i16)g;
         L.dn_shift[i] = (i8)shift;
     }
-    for (int k = lane(); k < N / 8; k += LANES) {
+    for (int k = lane(); k < FRAME / 8; k += LANES) {
         int b = 0;
 #pragma unroll
         for (int i = 1; i < NB; i++) b += k >= CLT_eband5ms[i];
@@ -1191,8 +1198,8 @@ CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int s
         wave_sync();
         return;
     }
-    const int bound = M8 * CLT_eband5ms[end];                   // zeros above the packet's end band (bands.c:179, :237)
-    if (LANES == 64) {
+    const int bound = CLT_eband5ms[end] << LM;                  // zeros above the packet's end band (bands.c:179, :237)
+    if (LANES == 64 && !ANY) {
         i32 xv[(FRAME + 63) / 64];
 #pragma unroll
         for (int m = 0; m < (FRAME + 63) / 64; m++) xv[m] = lane() + 64 * m < bound ? (i32)X[lane() + 64 * m] : 0;
@@ -1214,7 +1221,7 @@ CA_DEV void denormalise_bands_dec(S &L, const i16 *X, const i16 *bandLogE, int s
         for (int j = lane(); j < N; j += LANES) {
             i32 v = 0;
             if (j < bound) {
-                const int b = L.dn_band8[j >> 3];
+                const int b = L.dn_band8[j >> LM];
                 const i32 g = L.dn_gain[b];
                 const int shift = L.dn_shift[b];
                 v = shift < 0 ? shl32(mul16_16(X[j], g), -shift) : mul16_16(X[j], g) >> shift;
@@ -1270,6 +1277,9 @@ struct DecResult { int samples; u32 final_range; };
 // The TOC bytes this decoder takes (src/opus_decoder.c, opus_packet_parse_impl): CELT-only (0x80), 20 ms (3 << 3), code 0, any of
 // the four audio bandwidths (bits 5-6: NB, WB, SWB, FB) and mono or stereo (bit 2): 0x98 0xB8 0xD8 0xF8 / 0x9C 0xBC 0xDC 0xFC
 CA_DEV bool celt_toc_accepted(int toc) { return (toc & 0x9B) == 0x98; }
+// ... and the ones opusgpu_decode_batch_any takes: the frame size too is free (bits 3-4: 2.5, 5, 10, 20 ms = LM 0..3), 32 TOCs
+CA_DEV bool celt_toc_accepted_any(int toc) { return (toc & 0x83) == 0x80; }
+CA_DEV int celt_toc_LM(int toc) { return (toc >> 3) & 3; }
 CA_DEV int celt_toc_end(int toc) { const int bw = (toc >> 5) & 3; return bw == 0 ? 13 : bw == 1 ? 17 : bw == 2 ? 19 : 21; }   // src/opus_decoder.c:431-448
 CA_DEV int celt_toc_channels(int toc) { return (toc & 4) ? 2 : 1; }
 // what the stream remembers of its last TOC; the zeros of a fresh state read as fullband stereo (st->bandwidth == 0)
@@ -1289,7 +1299,9 @@ CA_DEV void celt_state_note_toc(opusgpu_celt_dec_state *st, int toc)
 // hand-off fields; st->mid_valid == 0 tells the later stages to leave this stream alone.
 // FBS: the caller knows the packet to be fullband stereo (TOC 0xFC); C and end are then the compile-time constants they were
 // before the other TOCs were taken, which is what the lane kernel runs when its whole wavefront holds such packets.
-template <bool FBS, class D>
+// ANY (opusgpu_decode_batch_any): the frame size comes from the TOC as well, LM = 0..3 for 120 << LM samples; without it LM is the
+// constant 3 and every line below is the code it was before the short frames were taken.
+template <bool FBS, bool ANY = false, class D>
 CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
 {
     DecResult res;
@@ -1298,22 +1310,24 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     st->mid_valid = 0;
     F.X = (x16_t *)st->mid_X;
     F.norm = (x16_t *)st->mid_norm;
-    const int N = FRAME, LM = LM3, M = M8;
     // len == 1 or 2: a payload of no or one byte is DTX (src/opus_decoder.c:245-251), the PLC entry point's business
     if (len < 3) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }
     const int toc = data[0];
-    if (!celt_toc_accepted(toc)) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
+    if (!(ANY ? celt_toc_accepted_any(toc) : celt_toc_accepted(toc))) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
+    const int LM = ANY && !FBS ? celt_toc_LM(toc) : (int)LM3, M = ANY && !FBS ? 1 << LM : (int)M8, N = ANY && !FBS ? (FRAME / M8) << LM : (int)FRAME;
     data++;
     len--;
     if (len > 1275) { res.samples = OPUSGPU_INVALID_PACKET; return res; }
     const int C = FBS ? 2 : celt_toc_channels(toc), end = FBS ? (int)NB : celt_toc_end(toc);
     celt_state_note_toc(st, toc);
     CA_COUNT(end == 13 ? "chbw_end13" : end == 17 ? "chbw_end17" : end == 19 ? "chbw_end19" : "chbw_end21", 1);
+    if (ANY) CA_COUNT(LM == 0 ? "fs_lm0" : LM == 1 ? "fs_lm1" : LM == 2 ? "fs_lm2" : "fs_lm3", 1);
     RangeDec dec;
     ec_dec_init(dec, data, (u32)len);
     i16 *oldBandE = st->oldBandE, *oldLogE = st->oldLogE, *oldLogE2 = st->oldLogE2, *backgroundLogE = st->backgroundLogE;
     if (C == 1) {                                                                               // celt_decoder.c:841-845
         CA_COUNT("chbw_mono", 1);
+        if (ANY && LM < 3) CA_COUNT(LM == 0 ? "fs_mono_lm0" : LM == 1 ? "fs_mono_lm1" : "fs_mono_lm2", 1);
         for (int i = 0; i < NB; i++) oldBandE[i] = (i16)imax(oldBandE[i], oldBandE[NB + i]);
     }
 
@@ -1342,17 +1356,18 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
         tell = ec_tell(dec);
     }
     int isTransient = 0;
-    if (tell + 3 <= total_bits) {
+    if (LM > 0 && tell + 3 <= total_bits) {                                                     // (a 2.5 ms frame has no transient flag)
         isTransient = ec_dec_bit_logp(dec, 3);
         tell = ec_tell(dec);
     }
+    if (ANY && isTransient) CA_COUNT(LM == 0 ? "fs_transient_lm0" : LM == 1 ? "fs_transient_lm1" : LM == 2 ? "fs_transient_lm2" : "fs_transient_lm3", 1);
     const int shortBlocks = isTransient ? M : 0;
     if (tell + 3 > total_bits) CA_COUNT("corrupt_intra_skipped", 1);
     const int intra_ener = tell + 3 <= total_bits ? ec_dec_bit_logp(dec, 3) : 0;
     CA_STAMP_F(F, 0);
-    unquant_coarse_energy_dec(oldBandE, intra_ener, dec, C, end);
+    unquant_coarse_energy_dec<ANY>(oldBandE, intra_ener, dec, C, end, LM);
     CA_STAMP_F(F, 1);
-    tf_decode_dec(isTransient, F.tf_res, dec, end);
+    tf_decode_dec<ANY>(isTransient, F.tf_res, dec, end, LM);
     tell = ec_tell(dec);
     int spread_decision = SPREAD_NORMAL;
     if (tell + 4 <= total_bits) spread_decision = ec_dec_icdf(dec, CLT_spread_icdf, 5);
@@ -1384,13 +1399,13 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     i32 bits = ((len * 8) << BITRES) - (i32)ec_tell_frac(dec) - 1;
     const int anti_collapse_rsv = isTransient && LM >= 2 && bits >= ((LM + 2) << BITRES) ? (1 << BITRES) : 0;
     bits -= anti_collapse_rsv;
-    AllocOut al = compute_allocation_wave(F, dec, C, alloc_trim, 0, 0, bits, 0, 0, end);
+    AllocOut al = compute_allocation_wave<ANY>(F, dec, C, alloc_trim, 0, 0, bits, 0, 0, end, LM);
     unquant_fine_energy_dec(oldBandE, F.fine_quant, dec, C, end);
     CA_STAMP_F(F, 2);
 
     u32 rng = st->rng;
-    quant_all_bands_dec(F, dec, shortBlocks, spread_decision, al.dual_stereo, al.intensity,
-                        len * (8 << BITRES) - anti_collapse_rsv, al.balance, al.codedBands, &rng, C, end);
+    quant_all_bands_dec<ANY>(F, dec, shortBlocks, spread_decision, al.dual_stereo, al.intensity,
+                        len * (8 << BITRES) - anti_collapse_rsv, al.balance, al.codedBands, &rng, C, end, LM);
     st->rng = rng;
     CA_STAMP_F(F, 10);
     int anti_collapse_on = 0;
@@ -1399,7 +1414,8 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     if (anti_collapse_on) {
         CA_COUNT("corrupt_anti_collapse", 1);
         if (C == 1) CA_COUNT("chbw_mono_anti_collapse", 1);
-        anti_collapse_dec(F, oldBandE, oldLogE, oldLogE2, st->rng, C, end);
+        if (ANY && LM == 2) CA_COUNT("fs_anti_collapse_lm2", 1);
+        anti_collapse_dec<ANY>(F, oldBandE, oldLogE, oldLogE2, st->rng, C, end, LM);
     }
     if (silence) {
         if (C == 1) CA_COUNT("chbw_mono_silence", 1);
@@ -1419,9 +1435,19 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     st->postfilter_period = postfilter_pitch;                                                    // celt_decoder.c:1000-1011, LM != 0
     st->postfilter_gain = postfilter_gain;
     st->postfilter_tapset = postfilter_tapset;
-    st->postfilter_period_old = st->postfilter_period;
-    st->postfilter_gain_old = st->postfilter_gain;
-    st->postfilter_tapset_old = st->postfilter_tapset;
+    if (LM != 0) {
+        st->postfilter_period_old = st->postfilter_period;
+        st->postfilter_gain_old = st->postfilter_gain;
+        st->postfilter_tapset_old = st->postfilter_tapset;
+    } else {                                                                                     // a 2.5 ms frame: what was current becomes old
+        st->postfilter_period_old = st->mid_pf_period;
+        st->postfilter_gain_old = st->mid_pf_gain;
+        st->postfilter_tapset_old = st->mid_pf_tapset;
+    }
+    if (ANY) {
+        st->mid_LM = LM;
+        st->last_short = LM != LM3 ? LM + 1 : 0;
+    }
 
     if (C == 1)                                                                                  // celt_decoder.c:1027-1028
         for (int i = 0; i < NB; i++) oldBandE[NB + i] = oldBandE[i];
@@ -1521,6 +1547,59 @@ CA_DEV void celt_decode_synth(S &L, opusgpu_celt_dec_state *st)
     }
 }
 
+// Stage 2 of opusgpu_decode_batch_any: the same for a frame of N = 120 << LM samples (st->mid_LM, uniform over the wavefront):
+// the history moves by N, a frame without a transient is ONE transform of N bins (shift 3 - LM), a transient one M = 1 << LM
+// transforms of 120 bins side by side (celt_decoder.c:287-350: B, NB, shift).
+template <class S>
+CA_DEV void celt_decode_synth_any(S &L, opusgpu_celt_dec_state *st)
+{
+    if (!uni(st->mid_valid)) return;
+    const int LM = uni(st->mid_LM) & 3, N = (FRAME / M8) << LM;
+    const int isTransient = uni(st->mid_isTransient), silence = uni(st->mid_silence);
+    const int mono = uni(st->mid_mono), end = uni(celt_state_end(st));
+    // OPUS_MOVE(decode_mem, decode_mem + N, DECODE_BUFFER_SIZE - N + overlap/2): ascending 16-byte units, four per lane loaded before
+    // they are stored. The source runs N / 4 >= 30 units ahead of the destination, so a unit is never read after it was written.
+    {
+        typedef int hv4 __attribute__((vector_size(16)));
+        const int nq = (DEC_BUF - N + OVL / 2) / 4;
+        for (int c = 0; c < 2; c++) {
+            hv4 *dst = reinterpret_cast<hv4 *>(st->decode_mem[c]);
+            const hv4 *src = reinterpret_cast<const hv4 *>(st->decode_mem[c] + N);
+            for (int q0 = 0; q0 < nq; q0 += 4 * LANES) {
+                hv4 hv[4];
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                    if (q0 + lane() + LANES * m < nq) hv[m] = src[q0 + lane() + LANES * m];
+                wave_sync();
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                    if (q0 + lane() + LANES * m < nq) dst[q0 + lane() + LANES * m] = hv[m];
+                wave_sync();
+            }
+        }
+    }
+    wave_sync();
+    for (int c = 0; c < 2; c++) {
+        i32 *mem = st->decode_mem[c];
+        i32 *out_syn = mem + DEC_BUF - N;
+        denormalise_bands_dec<true>(L, st->mid_X + (mono ? 0 : c * N), st->oldBandE + (mono ? 0 : c * NB), silence, end, LM);
+        const MdctTab T3 = mdct_global_tab<3>();
+        if (LM == 0) {
+            mdct_backward_wave<3, 1>(L.freq, 1, L.f2, out_syn, T3, lane());
+        } else if (LM == 1) {
+            if (isTransient) mdct_backward_wave<3, 2>(L.freq, 1, L.f2, out_syn, T3, lane());
+            else mdct_backward_wave<2, 1>(L.freq, 1, L.f2, out_syn, mdct_global_tab<2>(), lane());
+        } else if (LM == 2) {
+            if (isTransient) mdct_backward_wave<3, 4>(L.freq, 1, L.f2, out_syn, T3, lane());
+            else mdct_backward_wave<1, 1>(L.freq, 1, L.f2, out_syn, mdct_global_tab<1>(), lane());
+        } else {
+            if (isTransient) mdct_backward_wave<3, 8>(L.freq, 1, L.f2, out_syn, T3, lane());
+            else mdct_backward_wave<0, 1>(L.freq, 1, L.f2, out_syn, mdct_global_tab<0>(), lane());
+        }
+        wave_sync();
+    }
+}
+
 // Stage 3 (one lane per (stream, channel)): the pitch post-filter in place on the synthesis output
 // (celt_decoder.c:983-998) and deemphasis to interleaved int16 (celt_decoder.c:183-285: coef0 = 27853, no
 // downsampling, no accumulation).
@@ -1545,6 +1624,35 @@ CA_DEV void celt_decode_post_channel(opusgpu_celt_dec_state *st, int c, i16 *pcm
     st->preemph_memD[c] = m;
 }
 
+// Stage 3 of opusgpu_decode_batch_any: N = 120 << st->mid_LM samples; a 2.5 ms frame is the cross-fade alone (celt_decoder.c:983-998)
+CA_DEV void celt_postfilter_channel_any(opusgpu_celt_dec_state *st, int c, int N)
+{
+    i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
+    comb_filter_inplace_dec(out_syn, st->mid_pf_period_old, st->mid_pf_period, 120, st->mid_pf_gain_old, st->mid_pf_gain,
+                            st->mid_pf_tapset_old, st->mid_pf_tapset);
+    if (N > 120)
+        comb_filter_inplace_dec(out_syn + 120, st->mid_pf_period, st->mid_pf_period_new, N - 120, st->mid_pf_gain, st->mid_pf_gain_new,
+                                st->mid_pf_tapset, st->mid_pf_tapset_new);
+}
+
+CA_DEV void celt_decode_post_channel_any(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+{
+    if (!st->mid_valid) return;
+    const int N = (FRAME / M8) << (st->mid_LM & 3);
+    celt_postfilter_channel_any(st, c, N);
+    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
+    i32 m = st->preemph_memD[c];
+    for (int j = 0; j < N; j++) {                                                                // the rest of the row is not written
+        i32 t = add32(out_syn[j], m);
+        m = mul16_32_q15(27853, t);
+        i32 v = pshr32(t, 12);
+        v = imax(v, -32768);
+        v = imin(v, 32767);
+        pcm[j * 2 + c] = (i16)v;
+    }
+    st->preemph_memD[c] = m;
+}
+
 // all three stages, for the host emulation
 template <class D, class S>
 CA_DEV DecResult celt_decode_frame(D &F, S &L, opusgpu_celt_dec_state *st, const u8 *data, int len, i16 *pcm)
@@ -1552,6 +1660,15 @@ CA_DEV DecResult celt_decode_frame(D &F, S &L, opusgpu_celt_dec_state *st, const
     DecResult r = celt_decode_front(F, st, data, len);
     celt_decode_synth(L, st);
     for (int c = 0; c < 2; c++) celt_decode_post_channel(st, c, pcm);
+    return r;
+}
+
+template <class D, class S>
+CA_DEV DecResult celt_decode_frame_any(D &F, S &L, opusgpu_celt_dec_state *st, const u8 *data, int len, i16 *pcm)
+{
+    DecResult r = celt_decode_front_as<false, true>(F, st, data, len);
+    celt_decode_synth_any(L, st);
+    for (int c = 0; c < 2; c++) celt_decode_post_channel_any(st, c, pcm);
     return r;
 }
 

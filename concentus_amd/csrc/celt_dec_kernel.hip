@@ -22,7 +22,9 @@ namespace ca {
 // celt_back_lane_kernel.hip)
 // PLC (opusgpu_decode_batch_plc): a stream whose packet is lost (len == NULL or len[k] == 0) or is a DTX packet (one or two bytes) is left to
 // the concealment kernels (celt_dec_plc_kernel.hip), which find it by st->mid_plc
-template <int A, bool PLC>
+// ANY (opusgpu_decode_batch_any, with PLC): the packets may be 2.5, 5, 10 or 20 ms long (celt_decode_front_as<FBS, true>); a lost
+// packet is concealed as a 20 ms frame (mid_LM = 3) unless the stream's last packet was a shorter one (last_short)
+template <int A, bool PLC, bool ANY = false>
 __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu_celt_dec_state *states, const u8 *__restrict__ packets,
                                                               int packet_stride, const int *__restrict__ len,
                                                               int *__restrict__ ret, u32 *__restrict__ rng, int n)
@@ -43,6 +45,8 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
         const bool lost = ln == 0 || dtx;
         states[k].mid_plc = lost ? OPUSGPU_PLC_LOST : OPUSGPU_PLC_NONE;
         if (lost) {
+            // (a DTX packet's TOC says 20 ms; a loss after a shorter packet is concealed in steps by celt_dec_plc_any_kernel)
+            if (ANY) { states[k].mid_LM = LM3; if (dtx) states[k].last_short = 0; }
             if (dtx) celt_plc_dtx_toc(states + k, toc);
             states[k].mid_valid = 0;
             states[k].final_range = 0;
@@ -64,8 +68,8 @@ __global__ __launch_bounds__(64 * (64 / A)) void celt_decode_lane_kernel(opusgpu
     const u8 *pkt = packets + (size_t)k * packet_stride;
     const bool other = ln < 2 || pkt[0] != 0xFC;
     DecResult r;
-    if (__builtin_amdgcn_ballot_w64(other) == 0) r = celt_decode_front_as<true>(F, states + k, pkt, ln);
-    else r = celt_decode_front_as<false>(F, states + k, pkt, ln);
+    if (__builtin_amdgcn_ballot_w64(other) == 0) r = celt_decode_front_as<true, ANY>(F, states + k, pkt, ln);
+    else r = celt_decode_front_as<false, ANY>(F, states + k, pkt, ln);
     ret[k] = r.samples;
     rng[k] = r.final_range;
 }
@@ -85,19 +89,17 @@ __device__ __forceinline__ void celt_postfilter_channel(opusgpu_celt_dec_state *
                             st->mid_pf_tapset, st->mid_pf_tapset_new);
 }
 
-__device__ __forceinline__ void celt_deemphasis_pair(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+// G groups of eight samples from j0 on (G = 4: the block of 32 above)
+template <int G>
+__device__ __forceinline__ void celt_deemphasis_block(const int4 *src, int j0, i32 &m, int c, i16 *pcm)
 {
-    const int N = FRAME;
-    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
-    i32 m = st->preemph_memD[c];
-    const int4 *src = reinterpret_cast<const int4 *>(out_syn);
-    for (int j0 = 0; j0 < N; j0 += 32) {
-        int4 in[8];
+    {
+        int4 in[2 * G];
 #pragma unroll
-        for (int q = 0; q < 8; q++) in[q] = src[(j0 >> 2) + q];
-        int4 res[4];
+        for (int q = 0; q < 2 * G; q++) in[q] = src[(j0 >> 2) + q];
+        int4 res[G];
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
+        for (int g = 0; g < G; g++) {
             const i32 w[8] = {in[2 * g].x, in[2 * g].y, in[2 * g].z, in[2 * g].w, in[2 * g + 1].x, in[2 * g + 1].y, in[2 * g + 1].z, in[2 * g + 1].w};
             u32 v[8], o[8];
 #pragma unroll
@@ -117,8 +119,30 @@ __device__ __forceinline__ void celt_deemphasis_pair(opusgpu_celt_dec_state *st,
             res[g] = make_int4((int)pr[0], (int)pr[1], (int)pr[2], (int)pr[3]);
         }
 #pragma unroll
-        for (int g = 0; g < 4; g++) *reinterpret_cast<int4 *>(pcm + 2 * (j0 + 8 * g + 4 * c)) = res[g];
+        for (int g = 0; g < G; g++) *reinterpret_cast<int4 *>(pcm + 2 * (j0 + 8 * g + 4 * c)) = res[g];
     }
+}
+
+__device__ __forceinline__ void celt_deemphasis_pair(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+{
+    const int N = FRAME;
+    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
+    i32 m = st->preemph_memD[c];
+    const int4 *src = reinterpret_cast<const int4 *>(out_syn);
+    for (int j0 = 0; j0 < N; j0 += 32) celt_deemphasis_block<4>(src, j0, m, c, pcm);
+    st->preemph_memD[c] = m;
+}
+
+// ... of a frame of N = 120, 240, 480 or 960 samples: blocks of 32, then the groups of eight that are left (N is a multiple of
+// eight, so every store is 16 bytes inside the first N sample pairs of the row; the rest of the row is not written)
+__device__ __forceinline__ void celt_deemphasis_pair_any(opusgpu_celt_dec_state *st, int c, i16 *pcm, int N)
+{
+    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
+    i32 m = st->preemph_memD[c];
+    const int4 *src = reinterpret_cast<const int4 *>(out_syn);
+    int j0 = 0;
+    for (; j0 + 32 <= N; j0 += 32) celt_deemphasis_block<4>(src, j0, m, c, pcm);
+    for (; j0 < N; j0 += 8) celt_deemphasis_block<1>(src, j0, m, c, pcm);
     st->preemph_memD[c] = m;
 }
 
@@ -160,6 +184,29 @@ __global__ __launch_bounds__(256) void celt_decode_post_plc_kernel(opusgpu_celt_
         deemph = true;
     }
     if (deemph) celt_deemphasis_pair(st, c, out);
+}
+
+// The post kernel of opusgpu_decode_batch_any: as above, a received stream over the N = 120 << mid_LM samples of its frame. A
+// concealed stream is a 20 ms frame (mid_LM == 3).
+__global__ __launch_bounds__(256) void celt_decode_post_any_kernel(opusgpu_celt_dec_state *states, i16 *__restrict__ pcm, int n)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = t >> 1, c = t & 1;
+    if (k >= n) return;
+    opusgpu_celt_dec_state *st = states + k;
+    i16 *out = pcm + (size_t)k * FRAME * 2;
+    const int plc = st->mid_plc;
+    if (plc == OPUSGPU_PLC_ZEROS) {
+        int4 *z = reinterpret_cast<int4 *>(out + c * FRAME);
+        for (int j = 0; j < FRAME * 2 / 16; j++) z[j] = make_int4(0, 0, 0, 0);
+    } else if (plc == OPUSGPU_PLC_PITCH) {
+        celt_plc_tail_channel(st, c);
+        celt_deemphasis_pair(st, c, out);
+    } else if (st->mid_valid) {
+        const int N = (FRAME / M8) << (st->mid_LM & 3);
+        celt_postfilter_channel_any(st, c, N);
+        celt_deemphasis_pair_any(st, c, out, N);
+    }
 }
 
 // fresh decoder state (opus_decoder_create + OPUS_RESET_STATE, celt_decoder.c:1177-1190)
@@ -224,10 +271,12 @@ extern "C" int opusgpu_celt_dec_state_init(void *d_states, int n_streams, void *
 }
 
 extern "C" void opusgpu_launch_dec_plc(void *states, int n, hipStream_t s);
+extern "C" void opusgpu_launch_dec_synth_any(void *states, int n, hipStream_t s);
+extern "C" void opusgpu_launch_dec_plc_any(void *states, int16_t *pcm, int n, hipStream_t s);
 
-// The pipeline of both batched entry points, arguments checked: the lane kernel, with PLC the concealment's wave-per-stream kernel
+// The pipeline of the batched entry points, arguments checked: the lane kernel, with PLC the concealment's wave-per-stream kernel
 // (it leaves at once on a received stream), the synthesis, and the post kernel of the matching kind; each in its timing bracket.
-template <bool PLC>
+template <bool PLC, bool ANY = false>
 static int decode_batch_launch(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len, int16_t *d_pcm,
                                int32_t *d_ret, uint32_t *d_rng, int n_streams, hipStream_t s)
 {
@@ -235,7 +284,7 @@ static int decode_batch_launch(void *d_states, const unsigned char *d_packets, i
     {
         const int a = opusgpu_lane_frames(32);          // (decoder lane kernel: 5.06 ms at 32 streams per wavefront, 5.39 ms at 64)
         const dim3 grid((n_streams + 63) / 64), block(64 * (64 / a));
-#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, PLC>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
+#define CA_LAUNCH(A) hipLaunchKernelGGL((ca::celt_decode_lane_kernel<A, PLC, ANY>), grid, block, 0, s, (opusgpu_celt_dec_state *)d_states, \
                                         d_packets, packet_stride, d_len, d_ret, d_rng, n_streams)
         if (a == 32) CA_LAUNCH(32);
         else CA_LAUNCH(64);
@@ -244,14 +293,16 @@ static int decode_batch_launch(void *d_states, const unsigned char *d_packets, i
     opusgpu_timing_end(slot, s);
     if (PLC) {
         slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_PLC, s);
-        opusgpu_launch_dec_plc(d_states, n_streams, s);
+        if (ANY) opusgpu_launch_dec_plc_any(d_states, d_pcm, n_streams, s);
+        else opusgpu_launch_dec_plc(d_states, n_streams, s);
         opusgpu_timing_end(slot, s);
     }
     slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_SYNTH, s);
-    opusgpu_launch_dec_synth(d_states, n_streams, s);
+    if (ANY) opusgpu_launch_dec_synth_any(d_states, n_streams, s);
+    else opusgpu_launch_dec_synth(d_states, n_streams, s);
     opusgpu_timing_end(slot, s);
     slot = opusgpu_timing_begin(OPUSGPU_KERNEL_DEC_POST, s);
-    const auto post = PLC ? ca::celt_decode_post_plc_kernel : ca::celt_decode_post_kernel;
+    const auto post = ANY ? ca::celt_decode_post_any_kernel : PLC ? ca::celt_decode_post_plc_kernel : ca::celt_decode_post_kernel;
     hipLaunchKernelGGL(post, dim3((2 * n_streams + 255) / 256), dim3(256), 0, s, (opusgpu_celt_dec_state *)d_states, d_pcm, n_streams);
     opusgpu_timing_end(slot, s);
     return opusgpu_check_launch();
@@ -278,4 +329,17 @@ extern "C" int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_p
     if (((uintptr_t)d_pcm & 15) != 0) return OPUSGPU_BAD_ARG;
     if (!d_len) { d_packets = nullptr; packet_stride = 0; }
     return decode_batch_launch<true>(d_states, d_packets, packet_stride, d_len, d_pcm, d_ret, d_rng, n_streams, (hipStream_t)stream);
+}
+
+// opusgpu_decode_batch_plc for every code-0 CELT-only packet: 2.5, 5, 10 and 20 ms frames, in any mix (include/opusgpu.h)
+extern "C" int opusgpu_decode_batch_any(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                                        int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *stream)
+{
+    if (n_streams < 0) return OPUSGPU_BAD_ARG;
+    if (n_streams == 0) return OPUSGPU_OK;
+    if (!d_states || !d_pcm || !d_ret || !d_rng) return OPUSGPU_BAD_ARG;
+    if (d_len && (!d_packets || packet_stride <= 0)) return OPUSGPU_BAD_ARG;
+    if (((uintptr_t)d_pcm & 15) != 0) return OPUSGPU_BAD_ARG;
+    if (!d_len) { d_packets = nullptr; packet_stride = 0; }
+    return decode_batch_launch<true, true>(d_states, d_packets, packet_stride, d_len, d_pcm, d_ret, d_rng, n_streams, (hipStream_t)stream);
 }

@@ -81,14 +81,16 @@ CA_DEV u32 pvq_u(int n, int k)                                                  
     return CLT_pvq_u_data[CLT_pvq_u_row[lo] + hi];
 }
 
-// ---- compute_allocation (rate.c:527-639 + :248-525), start 0, LM 3; end 21 unless the decoder passes its packet's ----
+// ---- compute_allocation (rate.c:527-639 + :248-525), start 0; end 21 and LM 3 unless the decoder passes its packet's ----
 struct AllocOut { int codedBands; i32 balance; int intensity; int dual_stereo; };
 
-template <class L, class EC>
+// (ANYLM: LM is the run-time argument lm; without it the constant 3, folded before this body is inlined anywhere)
+template <bool ANYLM = false, class L, class EC>
 CA_DEVFN AllocOut compute_allocation_wave(L &F, EC &ec, int C, int alloc_trim, int intensity_in,
-                                          int dual_stereo_in, i32 total, int prev, int signalBandwidth, const int end = NB)
+                                          int dual_stereo_in, i32 total, int prev, int signalBandwidth, const int end = NB,
+                                          const int lm = LM3)
 {
-    const int LM = LM3, start = 0, len = NB;
+    const int LM = ANYLM ? lm : (int)LM3, start = 0, len = NB;
     const i16 *eB = CLT_eband5ms;
     i32 *bits = F.pulses, *ebits = F.fine_quant, *fine_priority = F.fine_priority;
     AllocOut out;

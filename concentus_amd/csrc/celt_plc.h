@@ -293,10 +293,13 @@ CA_DEV u32 plc_lcg_jump(u32 seed, int n)
 }
 
 // Stage 1 of a lost frame (see the head of this file). In: st->mid_plc == OPUSGPU_PLC_LOST; out: st->mid_plc = what is still owed.
-template <class L>
-CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
+// ANYN (opusgpu_decode_batch_any after a short packet): the concealed frame is n = 120 << lm samples, celt_decode_lost(st, N, LM);
+// without it N = 960 and LM = 3 are the constants they were.
+template <bool ANYN = false, class L>
+CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st, const int n = FRAME, const int lm = LM3)
 {
     if (uni(st->mid_plc) != OPUSGPU_PLC_LOST) return;
+    const int N = ANYN ? n : (int)FRAME, MM = ANYN ? 1 << lm : (int)M8;
     if (!uni(st->started)) {
         // no packet decoded yet: zeros, and the state stays as it is (src/opus_decoder.c:261-268)
         CA_COUNT("plc_no_history", 1);
@@ -320,9 +323,9 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
         for (int b = lane(); b < 2 * NB; b += LANES) {
             const int c = b >= NB, i = b - c * NB;
             if (i >= end) continue;
-            const int first = M8 * CLT_eband5ms[i], blen = M8 * (CLT_eband5ms[i + 1] - CLT_eband5ms[i]);
-            x16_t *X = (x16_t *)st->mid_X + c * FRAME + first;
-            u32 seed = plc_lcg_jump(seed0, c * M8 * CLT_eband5ms[end] + first);
+            const int first = MM * CLT_eband5ms[i], blen = MM * (CLT_eband5ms[i + 1] - CLT_eband5ms[i]);
+            x16_t *X = (x16_t *)st->mid_X + c * N + first;
+            u32 seed = plc_lcg_jump(seed0, c * MM * CLT_eband5ms[end] + first);
             for (int j = 0; j < blen; j++) {
                 seed = celt_lcg_rand(seed);
                 X[j] = (i16)((i32)seed >> 20);
@@ -331,7 +334,8 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
         }
         wave_sync();
         if (lane() == 0) {
-            st->rng = plc_lcg_jump(seed0, 2 * M8 * CLT_eband5ms[end]);
+            st->rng = plc_lcg_jump(seed0, 2 * MM * CLT_eband5ms[end]);
+            if (ANYN) st->mid_LM = lm;
             st->mid_valid = 1;
             st->mid_isTransient = 0;
             st->mid_silence = 0;
@@ -409,7 +413,20 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
             }
         }
         // OPUS_MOVE(buf, buf + N, DECODE_BUFFER_SIZE - N)
-        if (LANES == 64) {
+        if (ANYN) {
+            // ascending blocks of four loads, then their stores: the source runs N >= 120 ahead, so nothing is read after it was written
+            for (int k0 = 0; k0 < DEC_BUF - N; k0 += 4 * LANES) {
+                i32 hv[4];
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                    if (k0 + lane() + LANES * m < DEC_BUF - N) hv[m] = buf[N + k0 + lane() + LANES * m];
+                wave_sync();
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                    if (k0 + lane() + LANES * m < DEC_BUF - N) buf[k0 + lane() + LANES * m] = hv[m];
+                wave_sync();
+            }
+        } else if (LANES == 64) {
             enum { NM = (DEC_BUF - FRAME) / 64 };
             static_assert((DEC_BUF - FRAME) % 64 == 0, "history move in whole wavefronts");
             i32 hv[NM];
@@ -425,9 +442,9 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
         // the excitation repeated with period pitch_index, and the energy S1 of the signal it came from (celt_decoder.c:613-635:
         // after the move that signal is what raw[] holds)
         i32 s1 = 0;
-        for (int i = lane(); i < PLC_EXT; i += LANES) {
+        for (int i = lane(); i < N + OVL; i += LANES) {
             const int p = i / pitch_index, j = i - p * pitch_index;
-            buf[DEC_BUF - FRAME + i] = shl32(mul16_16_q15(P.att[p], P.exc[off + j]), 12);
+            buf[DEC_BUF - N + i] = shl32(mul16_16_q15(P.att[p], P.exc[off + j]), 12);
             const i32 t = raw[off + j];
             s1 = add32(s1, mul16_16(t, t) >> 8);
         }
@@ -445,10 +462,13 @@ CA_DEVFN void celt_plc_wave(L &P, opusgpu_celt_dec_state *st)
 // Stage 2 of the pitch-based branch for one channel (celt_decoder.c:637-704): celt_iir over the 1080 extrapolated samples, the
 // explosion check, the pre-filter on the overlap and the TDAC fold. etmp lives in the stream's mid_X row, which a lost frame
 // does not use otherwise.
-CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c)
+// ANYN: over n + 120 samples (a multiple of LPC_ORD for n = 120, 240, 480 too)
+template <bool ANYN = false>
+CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c, const int n = FRAME)
 {
+    const int EXT = ANYN ? n + OVL : (int)PLC_EXT;
     i32 *buf = st->decode_mem[c];
-    i32 *x = buf + DEC_BUF - FRAME;
+    i32 *x = buf + DEC_BUF - (EXT - OVL);
     // celt_iir (celt_lpc.c:151-230, the unrolled form): the filter's memory holds the NEGATED outputs as opus_val16
     i32 den[LPC_ORD], m[LPC_ORD];
 #pragma unroll
@@ -457,7 +477,7 @@ CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c)
         m[LPC_ORD - 1 - k] = (i16)neg32((i16)pshr32(x[-1 - k], 12));
     }
     i32 S2 = 0;
-    for (int i0 = 0; i0 < PLC_EXT; i0 += LPC_ORD) {
+    for (int i0 = 0; i0 < EXT; i0 += LPC_ORD) {
         i32 in[LPC_ORD];
 #pragma unroll
         for (int u = 0; u < LPC_ORD; u++) in[u] = x[i0 + u];
@@ -478,7 +498,7 @@ CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c)
     const i32 S1 = st->mid_plc_S1[c];
     if (!(S1 > (S2 >> 2))) {
         CA_COUNT("plc_explosion_zeroed", 1);
-        for (int i = 0; i < PLC_EXT; i++) x[i] = 0;
+        for (int i = 0; i < EXT; i++) x[i] = 0;
     } else if (S1 < S2) {
         CA_COUNT("plc_explosion_attenuated", 1);
         const i32 ratio = (i16)celt_sqrt(frac_div32(add32(S1 >> 1, 1), add32(S2, 1)));
@@ -486,7 +506,7 @@ CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c)
             const i32 tmp_g = (i16)(32767 - mul16_16_q15(CLT_window120[i], 32767 - ratio));
             x[i] = mul16_32_q15(tmp_g, x[i]);
         }
-        for (int i = OVL; i < PLC_EXT; i++) x[i] = mul16_32_q15(ratio, x[i]);
+        for (int i = OVL; i < EXT; i++) x[i] = mul16_32_q15(ratio, x[i]);
     }
     // comb_filter(etmp, buf + 2048, T, T, 120, -g, -g, tapset, tapset) (celt.c:183-244: g0 == g1, so the constant filter alone).
     // It looks back T + 2 samples from buf + 2048: T in [15, 1022] and tapset in [0, 2] whatever the state holds.
@@ -514,11 +534,11 @@ CA_DEV void celt_plc_tail_channel(opusgpu_celt_dec_state *st, int c)
 }
 
 // deemphasis (celt_decoder.c:183-285) of one channel, as at the end of celt_decode_post_channel
-CA_DEV void celt_deemphasis_channel(opusgpu_celt_dec_state *st, int c, i16 *pcm)
+CA_DEV void celt_deemphasis_channel(opusgpu_celt_dec_state *st, int c, i16 *pcm, const int N = FRAME)
 {
-    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - FRAME;
+    const i32 *out_syn = st->decode_mem[c] + DEC_BUF - N;
     i32 m = st->preemph_memD[c];
-    for (int j = 0; j < FRAME; j++) {
+    for (int j = 0; j < N; j++) {
         i32 t = add32(out_syn[j], m);
         m = mul16_32_q15(27853, t);
         i32 v = pshr32(t, 12);
@@ -583,6 +603,78 @@ CA_DEV DecResult celt_decode_lost_frame(LP_ &P, S &L, opusgpu_celt_dec_state *st
     DecResult r;
     r.samples = FRAME;
     r.final_range = st->final_range = 0;                                           // src/opus_decoder.c:579-580
+    return r;
+}
+
+// opusgpu_decode_batch_any: a lost packet is concealed as above when the stream's last packet was a 20 ms one (or none came yet).
+// After a packet of N < 960 samples the reference conceals the 960 samples in steps of N (src/opus_decoder.c:250 clamps the concealed
+// duration to the last packet's, :613-622 loops): 960 / N calls of celt_decode_lost(st, N, LM), each followed by its de-emphasis.
+// The steps depend on each other, so ONE wavefront (one "lane" in the emulation) does them all: celt_plc_wave, the synthesis
+// where the step is noise-based, and -- on lanes 0 and 1, one per channel -- the tail of the pitch-based branch and the
+// de-emphasis into the step's N sample pairs of the stream's row. st->last_short is LM + 1 of that last packet.
+template <class LP_, class S>
+CA_DEVFN void celt_plc_short_steps(LP_ &P, S &L, opusgpu_celt_dec_state *st, i16 *pcm)
+{
+    const int lm = (uni(st->last_short) - 1) & 3, N = (FRAME / M8) << lm;
+    CA_COUNT("fs_loss_after_short", 1);
+    for (int k = 0; k < FRAME / N; k++) {
+        const int loss_count = uni(st->loss_count);
+        const int noise = loss_count >= 5;
+        CA_COUNT(noise ? "fs_short_step_noise" : "fs_short_step_pitch", 1);
+        if (lane() == 0) st->mid_plc = OPUSGPU_PLC_LOST;
+        wave_sync();
+        celt_plc_wave<true>(P, st, N, lm);
+        wave_sync();
+        if (noise) celt_decode_synth_any(L, st);
+        wave_sync();
+        for (int c = lane(); c < 2; c += LANES) {
+            if (!noise) celt_plc_tail_channel<true>(st, c, N);
+            celt_deemphasis_channel(st, c, pcm + (size_t)k * N * 2, N);
+        }
+        wave_sync();
+    }
+    if (lane() == 0) {
+        st->mid_valid = 0;
+        st->mid_plc = OPUSGPU_PLC_DONE;
+        st->final_range = 0;
+    }
+}
+
+// a lost frame through the stages of opusgpu_decode_batch_any, for the host emulation (celt_plc_conceals was asked before)
+template <class LP_, class S>
+CA_DEV DecResult celt_decode_lost_frame_any(LP_ &P, S &L, opusgpu_celt_dec_state *st, i16 *pcm)
+{
+#if defined(CA_HOST_EMU)
+    const int dtx_toc = g_emu_dtx_toc;
+    g_emu_dtx_toc = -1;
+    if (dtx_toc < 0 && st->last_short != 0) {
+        celt_plc_short_steps(P, L, st, pcm);
+        DecResult r;
+        r.samples = FRAME;
+        r.final_range = 0;
+        return r;
+    }
+    if (dtx_toc >= 0) celt_plc_dtx_toc(st, dtx_toc);
+#endif
+    st->last_short = 0;                                                           // (a DTX packet's TOC says 20 ms)
+    st->mid_LM = LM3;
+    st->mid_valid = 0;
+    st->mid_plc = OPUSGPU_PLC_LOST;
+    celt_plc_wave(P, st);
+    celt_decode_synth_any(L, st);
+    for (int c = 0; c < 2; c++) {
+        if (st->mid_plc == OPUSGPU_PLC_ZEROS) {
+            for (int j = 0; j < FRAME; j++) pcm[j * 2 + c] = 0;
+        } else if (st->mid_plc == OPUSGPU_PLC_PITCH) {
+            celt_plc_tail_channel(st, c);
+            celt_deemphasis_channel(st, c, pcm);
+        } else {
+            celt_decode_post_channel_any(st, c, pcm);
+        }
+    }
+    DecResult r;
+    r.samples = FRAME;
+    r.final_range = st->final_range = 0;
     return r;
 }
 

@@ -62,7 +62,10 @@ typedef struct opusgpu_celt_state {
  * (src/opus_decoder.c:259-268): set by every decoded packet, cleared by init/reset; a loss before it is zeros.
  * `last_end` and `last_channels` are the Opus layer's st->bandwidth and st->stream_channels as the CELT decoder sees them
  * (src/opus_decoder.c:431-450, :683-686): the end band (13, 17, 19, 21) and the channel count (1, 2) of the last packet's TOC,
- * which a lost packet is concealed with. 0 (init / reset) reads as 21 / stereo. */
+ * which a lost packet is concealed with. 0 (init / reset) reads as 21 / stereo.
+ * `last_short` is the Opus layer's st->frame_size as far as it matters here (src/opus_decoder.c:250, :685): LM + 1 of the last
+ * packet opusgpu_decode_batch_any decoded when that was shorter than 20 ms, else 0. A loss after such a packet is concealed in
+ * steps of that packet's duration. Only opusgpu_decode_batch_any reads or writes it. */
 #define OPUSGPU_DECODE_BUFFER_SIZE 2048
 #define OPUSGPU_CELT_LPC_ORDER 24
 typedef struct opusgpu_celt_dec_state {
@@ -96,6 +99,11 @@ typedef struct opusgpu_celt_dec_state {
     int32_t mid_plc;
     int32_t mid_plc_S1[2];
     int32_t mid_mono;                                      /* the frame is one coded channel, synthesised into both (celt_decoder.c:313-325) */
+    /* ... of one opusgpu_decode_batch_any call: the frame is 120 << mid_LM samples (3 for a concealed one). The other entry
+     * points neither read nor write these four words. */
+    int32_t mid_LM;
+    int32_t last_short;
+    int32_t reserved_any[2];
 } opusgpu_celt_dec_state;
 
 /* mid_plc: the stream was received / is lost and not yet looked at / has no history (zeros) / is synthesised from noise by
@@ -105,6 +113,7 @@ typedef struct opusgpu_celt_dec_state {
 #define OPUSGPU_PLC_ZEROS 2
 #define OPUSGPU_PLC_NOISE 3
 #define OPUSGPU_PLC_PITCH 4
+#define OPUSGPU_PLC_DONE 5    /* opusgpu_decode_batch_any: concealed in steps and already written (celt_plc_short_steps) */
 
 #ifdef __cplusplus
 /* the synthesis kernel moves decode_mem in 16-byte units, and the records of a batch lie back to back */
@@ -112,6 +121,8 @@ static_assert(offsetof(opusgpu_celt_dec_state, decode_mem) % 16 == 0, "decode_me
 static_assert(sizeof(opusgpu_celt_dec_state) % 16 == 0, "sizeof(opusgpu_celt_dec_state) must stay a multiple of 16");
 static_assert(offsetof(opusgpu_celt_dec_state, last_end) == 52 && offsetof(opusgpu_celt_dec_state, oldBandE) == 64,
               "last_end / last_channels / final_range took the reserved words: no offset may move");
+static_assert(offsetof(opusgpu_celt_dec_state, mid_LM) == 24240 && sizeof(opusgpu_celt_dec_state) == 24256,
+              "mid_LM / last_short were appended behind mid_mono: no offset before them may move");
 #endif
 
 #ifdef __cplusplus

@@ -3,7 +3,8 @@
 The reference decodes one stream at a time: opus_decoder_create() -> opus_decode() per packet
 (opus-fix/include/opus.h:438-462, src/opus_decoder.c:121,758). `OpusDecoderBatch` keeps the same verbs over N
 streams whose state (overlap/history buffer, band energies, post-filter) lives in HBM; all computation happens
-in libopusgpu.so (opusgpu_decode_batch; opusgpu_decode_batch_plc when lost packets are to be concealed)."""
+in libopusgpu.so (opusgpu_decode_batch; opusgpu_decode_batch_plc when lost packets are to be concealed; opusgpu_decode_batch_any
+when the packets may be shorter than 20 ms)."""
 from . import lib as _lib
 
 OPUS_GET_FINAL_RANGE_REQUEST = 4031
@@ -27,7 +28,7 @@ class OpusDecoderBatch:
         _lib.check(_lib.load().opusgpu_celt_dec_state_init(self._states.data_ptr(), self.n, _lib.current_stream_handle()),
                    "opusgpu_celt_dec_state_init")
 
-    def decode(self, packets, lengths, conceal=False):
+    def decode(self, packets, lengths, conceal=False, any_frame_size=False, out=None):
         """opus_decode(dec, data, len, pcm, 960, 0) for every stream: packets uint8 [N][stride], lengths int32 [N].
         Returns (pcm int16 [N][960][2], ret int32 [N] = 960 or a negative error per stream).
         Accepted are CELT-only 20 ms single-frame packets, mono or stereo, NB / WB / SWB / FB (TOC 0x98 0xB8 0xD8 0xF8 /
@@ -35,20 +36,29 @@ class OpusDecoderBatch:
         TOC gives that stream -5.
         conceal=True (opusgpu_decode_batch_plc): a stream with length 0 lost its packet and is concealed
         (opus_decode(dec, NULL, 0, ...)) within the bandwidth of its last packet, as is a one-byte DTX packet with one of
-        those TOCs, whose bandwidth the stream takes first; its ret is 960 and its final range 0."""
+        those TOCs, whose bandwidth the stream takes first; its ret is 960 and its final range 0.
+        any_frame_size=True (opusgpu_decode_batch_any; implies conceal): frames of 2.5, 5, 10 and 20 ms, the 32 TOCs
+        0x80 | bw << 5 | fs << 3 | stereo << 2. ret is then 120, 240, 480 or 960, and only the first ret sample pairs of a
+        stream's row of pcm are written (out: a tensor [N][960][2] to write into instead of a fresh uninitialised one). A
+        one- or two-byte packet with a short-frame TOC gives -5 (see include/opusgpu.h)."""
         import torch
         if packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[0] != self.n or not packets.is_contiguous():
             raise ValueError("packets must be a contiguous uint8 tensor [streams][stride]")
         if lengths.dtype != torch.int32 or lengths.shape != (self.n,):
             raise ValueError("lengths must be int32 [streams]")
-        pcm = torch.empty((self.n, 960, 2), dtype=torch.int16, device=packets.device)
+        if out is None:
+            pcm = torch.empty((self.n, 960, 2), dtype=torch.int16, device=packets.device)
+        else:
+            if out.dtype != torch.int16 or out.shape != (self.n, 960, 2) or not out.is_contiguous() or out.device != packets.device:
+                raise ValueError("out must be a contiguous int16 tensor [streams][960][2] on the packets' device")
+            pcm = out
         ret = torch.empty((self.n,), dtype=torch.int32, device=packets.device)
         rng = torch.empty((self.n,), dtype=torch.int32, device=packets.device)
         L = _lib.load()
-        entry = L.opusgpu_decode_batch_plc if conceal else L.opusgpu_decode_batch
-        rc = entry(self._states.data_ptr(), packets.data_ptr(), packets.shape[1], lengths.data_ptr(),
-                   pcm.data_ptr(), ret.data_ptr(), rng.data_ptr(), self.n, _lib.current_stream_handle())
-        _lib.check(rc, "opusgpu_decode_batch_plc" if conceal else "opusgpu_decode_batch")
+        name = "opusgpu_decode_batch_any" if any_frame_size else "opusgpu_decode_batch_plc" if conceal else "opusgpu_decode_batch"
+        rc = getattr(L, name)(self._states.data_ptr(), packets.data_ptr(), packets.shape[1], lengths.data_ptr(),
+                              pcm.data_ptr(), ret.data_ptr(), rng.data_ptr(), self.n, _lib.current_stream_handle())
+        _lib.check(rc, name)
         self.final_range = rng
         return pcm, ret
 
@@ -71,9 +81,9 @@ class OpusDecoderBatch:
         raise _lib.OpusGpuError(-5, "opus_decoder_ctl request %d" % request)
 
 
-def decode_independent(packets, lengths):
+def decode_independent(packets, lengths, any_frame_size=False):
     """Decode every packet with its own fresh decoder (the first packet of its own stream); the packets may differ in
-    channel count and bandwidth (the TOCs of OpusDecoderBatch.decode)."""
+    channel count and bandwidth (the TOCs of OpusDecoderBatch.decode), with any_frame_size=True in frame size too."""
     dec = OpusDecoderBatch(packets.shape[0], device=packets.device)
-    pcm, ret = dec.decode(packets, lengths)
+    pcm, ret = dec.decode(packets, lengths, any_frame_size=any_frame_size)
     return pcm, ret, dec.final_range

@@ -68,6 +68,7 @@ SYMBOLS = [
     ("opusgpu_celt_dec_state_init", _i, [_vp, _i, _vp]),
     ("opusgpu_decode_batch", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     ("opusgpu_decode_batch_plc", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    ("opusgpu_decode_batch_any", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     ("opusgpu_decode_lost", _i, [_vp, _vp, _i]),
     ("opusgpu_encoder_create", _vp, [_i, _i, _i, _vp]),
     ("opusgpu_encoder_ctl", _i, None),          # variadic

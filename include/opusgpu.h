@@ -193,6 +193,25 @@ int opusgpu_decode_batch(void *d_states, const unsigned char *d_packets, int pac
  * One more launch than opusgpu_decode_batch (four); asynchronous on hip_stream, no allocation, no synchronisation inside. */
 int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
                              int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
+/* The same call for every code-0 CELT-only packet, frames of 2.5, 5, 10 and 20 ms: the 32 TOC bytes
+ *     0x80 | bw << 5 | fs << 3 | stereo << 2     bw 0..3 = NB WB SWB FB, fs 0..3 = 2.5 5 10 20 ms (120 << fs samples)
+ * i.e. the eight of opusgpu_decode_batch (fs = 3) and the 24 a RESTRICTED_LOWDELAY sender of shorter frames produces, decoded as
+ * opus_decode(st, data, len, pcm, 960, 0) does. The streams of one call may differ in frame size, channel count and bandwidth,
+ * and a stream may change all three from packet to packet. Arguments and behaviour of opusgpu_decode_batch_plc, except:
+ *   d_ret[i]   120, 240, 480 or 960 for a decoded packet (its TOC's frame size), 960 for a concealed one, or a negative code.
+ *   d_pcm      stays int16 [n][960][2]: stream i's first d_ret[i] sample pairs are written and the rest of its row is left
+ *              untouched (the whole row of a stream with a negative d_ret).
+ * Corrupt bytes behind an accepted TOC decode as the reference decodes them. A lost packet (d_len[i] == 0, d_len == NULL) is
+ * concealed for 960 samples as opus_decode(st, NULL, 0, pcm, 960, 0) does: in one 20 ms step after a 20 ms packet, a concealed 20 ms
+ * frame or before any packet, and in 960 / N steps of celt_decode_lost after a packet of N < 960 samples (src/opus_decoder.c:250,
+ * :613-622). Those steps depend on each other and run inside the concealment kernel, one wavefront per such stream.
+ * Known gap: a packet of one or two bytes with a short-frame TOC (DTX; the reference conceals the TOC's own duration) gives
+ * OPUSGPU_UNIMPLEMENTED, state and final range untouched.
+ * A stream's state should see short packets through this entry point only (the other two do not know its last frame size).
+ * The single-stream opusgpu_decode and compat/libopus.so below still take 20 ms packets only.
+ * Four launches, asynchronous on hip_stream, no allocation, no synchronisation inside, capturable in a graph. */
+int opusgpu_decode_batch_any(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                             int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
 
 /* ---- libopus single-stream encoder API as a batch of one (plumbing; BASELINE config #1) --------------
  * Same verbs, argument meaning and return codes as opus_encoder_create / opus_encoder_ctl / opus_encode /
