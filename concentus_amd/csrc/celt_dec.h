@@ -1301,6 +1301,9 @@ CA_DEV void celt_state_note_toc(opusgpu_celt_dec_state *st, int toc)
 // before the other TOCs were taken, which is what the lane kernel runs when its whole wavefront holds such packets.
 // ANY (opusgpu_decode_batch_any): the frame size comes from the TOC as well, LM = 0..3 for 120 << LM samples; without it LM is the
 // constant 3 and every line below is the code it was before the short frames were taken.
+template <bool FBS, bool ANY, class D>
+CA_DEV DecResult celt_decode_front_payload(D &F, opusgpu_celt_dec_state *st, DecResult res, const int toc, const u8 *data, int len);
+
 template <bool FBS, bool ANY = false, class D>
 CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
 {
@@ -1314,9 +1317,16 @@ CA_DEV DecResult celt_decode_front_as(D &F, opusgpu_celt_dec_state *st, const u8
     if (len < 3) { res.samples = len < 1 ? OPUSGPU_BAD_ARG : OPUSGPU_UNIMPLEMENTED; return res; }
     const int toc = data[0];
     if (!(ANY ? celt_toc_accepted_any(toc) : celt_toc_accepted(toc))) { res.samples = OPUSGPU_UNIMPLEMENTED; return res; }
+    return celt_decode_front_payload<FBS, ANY>(F, st, res, toc, data + 1, len - 1);
+}
+
+// ... from behind the TOC byte on: celt_decode_with_ec (celt/celt_decoder.c:713) on the len bytes of one frame's payload, under an
+// accepted TOC. res comes in as the caller's answer for a rejected packet. This is the whole of a code-0 packet behind its TOC
+// (celt_decode_front_as) and one frame of a multi-frame packet (celt_decode_front_frame).
+template <bool FBS, bool ANY, class D>
+CA_DEV DecResult celt_decode_front_payload(D &F, opusgpu_celt_dec_state *st, DecResult res, const int toc, const u8 *data, int len)
+{
     const int LM = ANY && !FBS ? celt_toc_LM(toc) : (int)LM3, M = ANY && !FBS ? 1 << LM : (int)M8, N = ANY && !FBS ? (FRAME / M8) << LM : (int)FRAME;
-    data++;
-    len--;
     if (len > 1275) { res.samples = OPUSGPU_INVALID_PACKET; return res; }
     const int C = FBS ? 2 : celt_toc_channels(toc), end = FBS ? (int)NB : celt_toc_end(toc);
     celt_state_note_toc(st, toc);
@@ -1480,6 +1490,21 @@ template <class D>
 CA_DEV DecResult celt_decode_front(D &F, opusgpu_celt_dec_state *st, const u8 *data, int len)
 {
     return celt_decode_front_as<false>(F, st, data, len);
+}
+
+// celt_decode_front_as<FBS, true> for one frame of a parsed packet (opus_packet.h), the TOC and the frame's payload apart: what
+// opus_decode_frame (src/opus_decoder.c:692) gets for frame f. The caller has accepted the TOC (celt_toc_accepted_any) and taken
+// the frames of at most one byte away (DTX, celt_plc.h).
+template <bool FBS, class D>
+CA_DEV DecResult celt_decode_front_frame(D &F, opusgpu_celt_dec_state *st, const int toc, const u8 *payload, int size)
+{
+    DecResult res;
+    res.samples = OPUSGPU_INVALID_PACKET;
+    res.final_range = st->final_range;
+    st->mid_valid = 0;
+    F.X = (x16_t *)st->mid_X;
+    F.norm = (x16_t *)st->mid_norm;
+    return celt_decode_front_payload<FBS, true>(F, st, res, toc, payload, size);
 }
 
 // Stage 2 (one wavefront per stream; LANES == 1 in the emulation): celt_synthesis (celt_decoder.c:287-350) for CC == 2 -- shift the

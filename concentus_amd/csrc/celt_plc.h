@@ -612,12 +612,15 @@ CA_DEV DecResult celt_decode_lost_frame(LP_ &P, S &L, opusgpu_celt_dec_state *st
 // The steps depend on each other, so ONE wavefront (one "lane" in the emulation) does them all: celt_plc_wave, the synthesis
 // where the step is noise-based, and -- on lanes 0 and 1, one per channel -- the tail of the pitch-based branch and the
 // de-emphasis into the step's N sample pairs of the stream's row. st->last_short is LM + 1 of that last packet.
-template <class LP_, class S>
-CA_DEVFN void celt_plc_short_steps(LP_ &P, S &L, opusgpu_celt_dec_state *st, i16 *pcm)
+// GIVEN (opusgpu_decode_batch_packets, a DTX frame under a short-frame TOC): the caller names the step's size, lm_given, and how many
+// steps, steps_given -- one, the TOC's own duration (src/opus_decoder.c:250 with st->frame_size already the packet's, :685).
+template <bool GIVEN = false, class LP_, class S>
+CA_DEVFN void celt_plc_short_steps(LP_ &P, S &L, opusgpu_celt_dec_state *st, i16 *pcm, const int lm_given = 0, const int steps_given = 0)
 {
-    const int lm = (uni(st->last_short) - 1) & 3, N = (FRAME / M8) << lm;
-    CA_COUNT("fs_loss_after_short", 1);
-    for (int k = 0; k < FRAME / N; k++) {
+    const int lm = GIVEN ? lm_given & 3 : (uni(st->last_short) - 1) & 3, N = (FRAME / M8) << lm;
+    const int steps = GIVEN ? steps_given : FRAME / N;
+    CA_COUNT(GIVEN ? "multi_dtx_short" : "fs_loss_after_short", 1);
+    for (int k = 0; k < steps; k++) {
         const int loss_count = uni(st->loss_count);
         const int noise = loss_count >= 5;
         CA_COUNT(noise ? "fs_short_step_noise" : "fs_short_step_pitch", 1);

@@ -69,6 +69,8 @@ SYMBOLS = [
     ("opusgpu_decode_batch", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     ("opusgpu_decode_batch_plc", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     ("opusgpu_decode_batch_any", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    ("opusgpu_packet_parse_batch", _i, [_vp, _i, _vp, _vp, _i, _vp]),
+    ("opusgpu_decode_batch_packets", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     ("opusgpu_decode_lost", _i, [_vp, _vp, _i]),
     ("opusgpu_encoder_create", _vp, [_i, _i, _i, _vp]),
     ("opusgpu_encoder_ctl", _i, None),          # variadic

@@ -205,13 +205,70 @@ int opusgpu_decode_batch_plc(void *d_states, const unsigned char *d_packets, int
  * concealed for 960 samples as opus_decode(st, NULL, 0, pcm, 960, 0) does: in one 20 ms step after a 20 ms packet, a concealed 20 ms
  * frame or before any packet, and in 960 / N steps of celt_decode_lost after a packet of N < 960 samples (src/opus_decoder.c:250,
  * :613-622). Those steps depend on each other and run inside the concealment kernel, one wavefront per such stream.
- * Known gap: a packet of one or two bytes with a short-frame TOC (DTX; the reference conceals the TOC's own duration) gives
- * OPUSGPU_UNIMPLEMENTED, state and final range untouched.
- * A stream's state should see short packets through this entry point only (the other two do not know its last frame size).
+ * A packet of one or two bytes with a short-frame TOC (DTX; the reference conceals the TOC's own duration) gives
+ * OPUSGPU_UNIMPLEMENTED here, state and final range untouched, as do the frame-count codes 1-3: opusgpu_decode_batch_packets
+ * below takes both.
+ * A stream's state should see short packets through this entry point and opusgpu_decode_batch_packets only (the other two do not
+ * know its last frame size).
  * The single-stream opusgpu_decode and compat/libopus.so below still take 20 ms packets only.
  * Four launches, asynchronous on hip_stream, no allocation, no synchronisation inside, capturable in a graph. */
 int opusgpu_decode_batch_any(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
                              int16_t *d_pcm, int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
+
+/* ---- the Opus packet layer, batched: opus_packet_parse() (opus-fix/src/opus.c:190-353) ------------------------------------------
+ * One record per stream, in device memory, written by one lane per stream:
+ *   ret            the packet's frame count 1..48; 0 for d_len[i] == 0 (a lost packet); OPUSGPU_INVALID_PACKET where
+ *                  opus_packet_parse returns OPUS_INVALID_PACKET; OPUSGPU_BAD_ARG for d_len[i] < 0, d_len[i] > packet_stride
+ *                  or d_len[i] > 32767 (such a row is not read). The last is this library's limit, not the reference's: the
+ *                  16-bit offsets below address 32767 bytes, so a longer packet -- legal Opus only with kilobytes of padding
+ *                  or with 48 frames of more than 680 bytes each -- is refused rather than parsed into offsets that wrap.
+ *   frame_samples  opus_packet_get_samples_per_frame(data, 48000): 120, 240, 480, 960 for a CELT-only TOC, up to 2880 for SILK.
+ *   toc            the packet's first byte. SILK and hybrid TOCs are parsed like any other: this is the whole of opus_packet_parse.
+ *   offset, size   frame f lies at offset[f] from the start of the packet and has size[f] bytes, 0..1275; zero from frame `ret` on
+ *                  and throughout for ret <= 0.
+ *   pad_           0 (opusgpu_decode_batch_packets keeps its per-stream decision here while it runs).
+ * Every rule of the reference's parser holds: code 1 needs an even payload; code 2 and VBR code 3 read one- or two-byte frame
+ * lengths; code 3 rejects a count of 0 and more than 120 ms; the padding chain; a CBR payload divides by the count; no frame is
+ * longer than 1275 bytes; the remaining length never goes negative. No byte at or behind d_len[i] is read. */
+typedef struct opusgpu_packet_frames {
+    int32_t  ret;
+    int16_t  frame_samples;
+    uint8_t  toc, pad_;
+    int16_t  offset[48];
+    int16_t  size[48];
+} opusgpu_packet_frames;
+int opusgpu_packet_parse_batch(const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                               opusgpu_packet_frames *d_frames, int n_streams, void *hip_stream);
+
+/* opus_decode(st, data, len, pcm, frame_size, 0) for every CELT-only packet: the 32 TOCs of opusgpu_decode_batch_any with any
+ * frame-count code -- one frame (code 0), two (codes 1, 2), 1..48 CBR or VBR with or without padding (code 3) --, as a libopus
+ * encoder given 40 or 60 ms per call, opus_repacketizer_* and opus_packet_pad produce them. Arguments of opusgpu_decode_batch_any,
+ * except:
+ *   d_pcm       int16 [n][frame_size][2], 16-byte aligned. frame_size is opus_decode's: a multiple of 120 in 960..5760
+ *               (OPUSGPU_BAD_ARG for the call otherwise; the floor keeps the 960 samples of a concealed lost packet inside the row).
+ *   max_frames  1..48: how many frame passes the call launches (4 launches each, after the parse). The frame counts differ per
+ *               stream and stay on the device, so the caller bounds them: a packet of more frames gives that stream
+ *               OPUSGPU_UNIMPLEMENTED. That is this library's limit, not the reference's; 48 takes every packet of at most 32767 bytes.
+ *   d_frames    device scratch, n_streams records, filled by the parse, which is the call's first launch.
+ *   d_ret[i]    count * frame_samples for a decoded packet: the first d_ret[i] sample pairs of the row are written, frame f at
+ *               f * frame_samples, the rest is untouched. 960 for a lost packet (d_len[i] == 0 or d_len == NULL), concealed as
+ *               opusgpu_decode_batch_any does. OPUSGPU_INVALID_PACKET from the parser; then OPUSGPU_BUFFER_TOO_SMALL for
+ *               count * frame_samples > frame_size, as the reference orders the two; OPUSGPU_UNIMPLEMENTED for a SILK or hybrid
+ *               TOC and for count > max_frames; OPUSGPU_BAD_ARG for a length past packet_stride or past 32767 bytes. A rejected stream keeps its state
+ *               and its final range, and its row is not written: the decision falls once, before the first pass, so no packet is
+ *               ever half decoded.
+ *               (One exception, as in the reference's own loop, src/opus_decoder.c:693-694: should a frame inside an accepted
+ *               packet fail -- OPUSGPU_INTERNAL_ERROR, the range decoder past the frame's end; no input is known to reach it --
+ *               d_ret[i] is that error, the frames before it stay decoded and written, and the later ones are skipped.)
+ *   d_rng[i]    the final range after the LAST frame: 0 if that is a DTX frame (src/opus_decoder.c:579-580).
+ * A frame of at most one byte is a DTX frame (src/opus_decoder.c:245-251): after the stream has taken the TOC's bandwidth, channel
+ * count and frame size, frame_samples are concealed -- zeros before the first decoded frame of the stream, else one step of
+ * celt_decode_lost of exactly that size. This includes the one- and two-byte code-0 packets with a short-frame TOC.
+ * 1 + 4 * max_frames launches, asynchronous on hip_stream, no allocation, no synchronisation inside, capturable in a graph. With
+ * kernel timing on, the passes are summed under the four OPUSGPU_KERNEL_DEC_* ids; the parse is not timed. */
+int opusgpu_decode_batch_packets(void *d_states, const unsigned char *d_packets, int packet_stride, const int32_t *d_len,
+                                 int16_t *d_pcm, int frame_size, int max_frames, opusgpu_packet_frames *d_frames,
+                                 int32_t *d_ret, uint32_t *d_rng, int n_streams, void *hip_stream);
 
 /* ---- libopus single-stream encoder API as a batch of one (plumbing; BASELINE config #1) --------------
  * Same verbs, argument meaning and return codes as opus_encoder_create / opus_encoder_ctl / opus_encode /
