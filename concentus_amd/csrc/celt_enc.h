@@ -461,16 +461,16 @@ CA_DEVFN void celt_encode_front_phase(L &F, const opusgpu_celt_config &cfg, cons
     i32 temporal_vbr = 0;
     for (int mdct_pass = secondMdct ? 0 : 1;;) {
         CA_STAMP(5);
-        if constexpr (L::XF_CHANNELS == 1) {
-            // one coefficient buffer: a channel is transformed, measured and (except in the long-block pre-pass, whose only
-            // product is bandLogE2) normalised before the next one takes the buffer. Normalising here is speculative -- the
-            // transient patch below may order the frame transformed again, which simply repeats all of this with short blocks --
-            // and exact: a band's gain depends on that channel's own band energy only (bands.c:146-168).
-            for (int c = 0; c < C; c++) {
-                compute_mdct_channel(F, c, mdct_pass == 0 ? 0 : shortBlocks);
-                band_energies_channel(F, c, mdct_pass == 0 ? F.bandLogE2 : F.bandLogE);
-                if (mdct_pass != 0) normalise_bands_channel(F, c);
-            }
+        if (mdct_pass == 2) CA_COUNT("front_mdct_redo", 1);
+        else if (mdct_pass == 1 && shortBlocks) CA_COUNT("front_mdct_short", 1);
+        if constexpr (L::JOINT_CHANNELS) {
+            // both channels together, the coefficients in the FFT scratch itself: transformed, measured and (except in the
+            // long-block pre-pass, whose only product is bandLogE2) normalised straight into FrameMid::X. Normalising here is
+            // speculative -- the transient patch below may order the frame transformed again, which simply repeats all of this
+            // with short blocks -- and exact: a band's gain depends on that channel's own band energy only (bands.c:146-168).
+            compute_mdcts_joint(F, mdct_pass == 0 ? 0 : shortBlocks);
+            band_energies_joint(F, mdct_pass == 0 ? F.bandLogE2 : F.bandLogE);
+            if (mdct_pass != 0) normalise_bands_joint(F);
         } else {
             compute_mdcts_wave(F, fc, mdct_pass == 0 ? 0 : shortBlocks);
             CA_STAMP(30);
@@ -489,7 +489,7 @@ CA_DEVFN void celt_encode_front_phase(L &F, const opusgpu_celt_config &cfg, cons
             tf_estimate = 3277;                                  // QCONST16(.2f,14)
             break;
         }
-        if constexpr (L::XF_CHANNELS != 1) CA_TAP("freq", F.xf, sizeof(F.xf));
+        if constexpr (!L::JOINT_CHANNELS) CA_TAP("freq", F.xf, sizeof(F.xf));
         CA_TAP("bandE", F.bandE, sizeof(F.bandE)); CA_TAP("bandLogE", F.bandLogE, sizeof(F.bandLogE));
         {   // temporal VBR (celt_encoder.c:1803-1819)
             i32 follow = -10240;
@@ -541,7 +541,7 @@ CA_DEVFN void celt_encode_front_phase(L &F, const opusgpu_celt_config &cfg, cons
 
     CA_STAMP(5);
     // 10. normalise
-    if constexpr (L::XF_CHANNELS != 1) normalise_bands_wave(F, fc);
+    if constexpr (!L::JOINT_CHANNELS) normalise_bands_wave(F, fc);
 
     if constexpr (!L::IN_IS_GLOBAL) CA_TAP("X", F.in, 2 * FRAME * 2);
     CA_STAMP(6);

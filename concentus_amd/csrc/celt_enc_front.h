@@ -44,7 +44,7 @@ template <class P, class V> CA_DEV void st0(P p, V v) { if (lane() == 0) *p = v;
 //         wave), which lets 16 waves share a CU and overlap their serial, latency-bound chains.
 // The hand-off between them is the pointer-free FrameMid record in HBM (celt_enc.h).
 struct __attribute__((aligned(16))) FrontLds {
-    enum { IN_IS_GLOBAL = 0, XF_CHANNELS = 2 };
+    enum { IN_IS_GLOBAL = 0, JOINT_CHANNELS = 0 };
     i32 in[2][FRAME + OVL];        // overlap + pre-emphasised (then comb-filtered) signal; finally X[2][960] (i16)
     i32 xf[2][FRAME];              // dc-rejected PCM (i16) -> unfiltered pre-emphasised samples -> MDCT coefficients
     union {
@@ -110,7 +110,7 @@ struct __attribute__((aligned(16))) BackLds {
 // go straight to the HBM hand-off buffer, and the normalised bands X are written straight into FrameMid.
 // 14.4 KB / 12.7 KB instead of 22.8 KB -> 11 / 12 waves per CU instead of 7.
 struct __attribute__((aligned(16))) Front1Lds {
-    enum { IN_IS_GLOBAL = 1, XF_CHANNELS = 2 };
+    enum { IN_IS_GLOBAL = 1, JOINT_CHANNELS = 0 };
     i32 *in_g;                     // -> in_ws[2][1080] of this frame
     i32 xf[2][FRAME];
     union {
@@ -125,17 +125,21 @@ struct __attribute__((aligned(16))) Front1Lds {
 };
 
 struct __attribute__((aligned(16))) Front2Lds {
-    // XF_CHANNELS 1 (round 3): ONE channel's MDCT coefficients at a time. Transform, band energies and normalisation of a
-    // channel need nothing of the other one, so the channels go through the same buffer one after the other and the
-    // normalised bands leave for FrameMid::X at once (celt_encode_front_phase). 8.7 KB instead of 12.5 KB of LDS per
-    // wavefront: four wavefronts per SIMD (the register budget's limit) instead of three.
-    enum { IN_IS_GLOBAL = 1, XF_CHANNELS = 1 };
+    // JOINT_CHANNELS: both channels go through transform, band energies and normalisation TOGETHER, every lane loop over one
+    // index space of the two (mdct_forward_wave2, band_energies_joint, normalise_bands_joint), so that the partly filled
+    // last trip of a loop is paid once per frame, not once per channel. The transform works in place: a channel's FFT
+    // scratch (int2[480]) IS its coefficient row (i32[960]) afterwards, and the normalised bands leave for FrameMid::X at
+    // once (celt_encode_front_phase). 9.3 KB of LDS per wavefront, where a coefficient row per channel next to the
+    // scratch took 12.5 KB: four wavefronts per SIMD (the register budget's limit) instead of three.
+    enum { IN_IS_GLOBAL = 1, JOINT_CHANNELS = 1 };
     i32 *in_g;                     // -> in_ws[2][1080] of this frame (read only here)
     i16 *x_g;                      // -> FrameMid::X of this frame
-    i32 xf[1][FRAME];
     union {
-        int2 f2[480];
+        int2 f2[2][FFT_CH_STRIDE]; // FFT scratch of channel c
+        i32 xf[2][FRAME];          // ... which holds its MDCT coefficients once the transform is done
     } s;
+    i32 red[200];                  // band_energies_joint: a partial result per chunk of eight bins
+    i16 eshift[2 * NB];            //                      the shift of a band
     u8 packet[64];
     i32 bandE[2 * NB];
     i16 bandLogE[2 * NB], bandLogE2[2 * NB];
@@ -937,8 +941,7 @@ CA_DEVFN TransientOut transient_analysis_wave(L &F, const FrameCtx &fc)
 }
 
 // ---- MDCTs of one frame (compute_mdcts, celt_encoder.c:418-461): in -> xf (as freq) ------------------
-// where channel c's coefficients live: its own row, or THE row of a one-channel working set
-template <class L> CA_DEV i32 *xf_row(L &F, int c) { return F.xf[L::XF_CHANNELS == 1 ? 0 : c]; }
+template <class L> CA_DEV i32 *xf_row(L &F, int c) { return F.xf[c]; }
 
 template <class L>
 CA_DEVFN void compute_mdct_channel(L &F, int c, int shortBlocks)
@@ -1047,6 +1050,111 @@ template <class L>
 CA_DEVFN void normalise_bands_wave(L &F, const FrameCtx &fc)
 {
     for (int c = 0; c < fc.C; c++) normalise_bands_channel(F, c);
+}
+
+// ---- the same three stages on BOTH channels at once (JOINT_CHANNELS working sets, stereo) ---------------------------------
+// Every loop of the per-channel routines above, over one index space of the two channels: 2 x 100 chunks, 2 x NB bands,
+// 2 x 800 bins. Entry q of such a space belongs to channel q / n (a compare: there are two), and everything a channel's
+// entry computes is what the per-channel routine computes for it, bit for bit.
+template <class L>
+CA_DEVFN void compute_mdcts_joint(L &F, int shortBlocks)
+{
+    if (shortBlocks) {
+        const MdctTab T = mdct_global_tab<3>();
+        mdct_forward_wave2<3, 8>(tsig(F, 0), FRAME + OVL, F.s.f2[0], T, lane());
+    } else {
+        const MdctTab T = mdct_global_tab<0>();
+        mdct_forward_wave2<0, 1>(tsig(F, 0), FRAME + OVL, F.s.f2[0], T, lane());
+    }
+}
+
+// compute_band_energies + amp2Log2, see band_energies_channel. The FFT scratch is not free here (it holds the coefficients),
+// so the partial results have an array of their own, and a small one: a chunk leaves ONE word for the first reduction, the
+// largest magnitude of its eight bins as an unsigned number, which the chunk's sum of squares overwrites later. The
+// reference's maxval is MAX32(max, -min) in wrapping arithmetic: that IS the largest unsigned magnitude unless some bin
+// holds -2^31, whose negation wraps back to itself and loses to every max >= 0. Then (magnitude 2^31: no signal reaches
+// it, but equality is not argued from signals) the band's own lane finds the plain maximum by walking the band.
+template <class L>
+CA_DEVFN void band_energies_joint(L &F, i16 *bandLogE)
+{
+    const i32 *X = F.s.xf[0];                                   // channel c's bin j: X[c * FRAME + j]
+    i32 *red = F.red;
+    constexpr int NCH = 100;                                    // chunks per channel
+    for (int q = lane(); q < 2 * NCH; q += LANES) {
+        const int c = q >= NCH ? 1 : 0;
+        const i32 *x = X + c * (FRAME - 8 * NCH) + 8 * q;       // = X + c * FRAME + 8 * (q - c * NCH)
+        i32 mx = 0, mn = 0;
+#pragma unroll
+        for (int u = 0; u < 8; u++) { const i32 v = x[u]; mx = imax(mx, v); mn = imin(mn, v); }
+        const u32 neg = 0u - (u32)mn;                           // |mn| as an unsigned number, 2^31 included
+        red[q] = (i32)((u32)mx > neg ? (u32)mx : neg);
+    }
+    wave_sync();
+    for (int k = lane(); k < 2 * NB; k += LANES) {
+        const int c = k >= NB ? 1 : 0, b = k - c * NB;
+        u32 mag = 0;
+        for (int ch = CLT_eband5ms[b]; ch < CLT_eband5ms[b + 1]; ch++) { const u32 m = (u32)red[c * NCH + ch]; mag = m > mag ? m : mag; }
+        i32 maxval = (i32)mag;
+        if (mag == 0x80000000u) {
+            maxval = 0;
+            for (int j = CLT_eband5ms[b] << LM3; j < (CLT_eband5ms[b + 1] << LM3); j++) maxval = imax(maxval, X[c * FRAME + j]);
+        }
+        // shift of the band, or "no energy" (bands.c:108-126)
+        F.eshift[k] = (i16)(maxval > 0 ? celt_ilog2(maxval) - 14 + (((CLT_logN400[b] >> 3) + LM3 + 1) >> 1) : 0x7fff);
+    }
+    wave_sync();
+    for (int q = lane(); q < 2 * NCH; q += LANES) {
+        const int c = q >= NCH ? 1 : 0;
+        const i32 *x = X + c * (FRAME - 8 * NCH) + 8 * q;
+        const int shift = F.eshift[CLT_bin2band[q - c * NCH] + c * NB];
+        i32 sum = 0;
+        if (shift != 0x7fff) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const i32 xv = x[u];
+                const i32 v = shift > 0 ? (i16)(xv >> shift) : (i16)shl32(xv, -shift);
+                sum = mac16_16(sum, v, v);
+            }
+        }
+        red[q] = sum;
+    }
+    wave_sync();
+    for (int k = lane(); k < 2 * NB; k += LANES) {
+        const int c = k >= NB ? 1 : 0, b = k - c * NB;
+        const int shift = F.eshift[k];
+        i32 E = 1;
+        if (shift != 0x7fff) {
+            i32 sum = 0;
+            for (int ch = CLT_eband5ms[b]; ch < CLT_eband5ms[b + 1]; ch++) sum = add32(sum, red[c * NCH + ch]);
+            E = add32(1, vshr32(celt_sqrt(sum), -shift));
+        }
+        F.bandE[k] = E;
+        bandLogE[k] = (i16)(celt_log2(shl32(E, 2)) - shl16(CLT_eMeans[b], 6));
+    }
+    wave_sync();
+}
+
+// normalise_bands, see normalise_bands_channel
+template <class L>
+CA_DEVFN void normalise_bands_joint(L &F)
+{
+    i16 *X = frame_X(F);
+    const i32 *xf = F.s.xf[0];
+    constexpr int NBIN = 800;                                   // CLT_eband5ms[NB] << LM3 bins per channel
+    for (int k = lane(); k < 2 * NB; k += LANES) {
+        i32 bE = F.bandE[k];
+        int shift = celt_zlog2(bE) - 13;
+        i32 E = (i16)vshr32(bE, shift);                                              // opus_val16 E
+        F.normg[k] = (i16)celt_rcp(shl32(E, 3));
+        F.normshift[k] = (i8)shift;
+    }
+    wave_sync();
+    for (int q = lane(); q < 2 * NBIN; q += LANES) {
+        const int c = q >= NBIN ? 1 : 0, j = q - c * NBIN;
+        int b = CLT_bin2band[j >> 3] + c * NB;
+        X[c * FRAME + j] = (i16)mul16_16_q15(vshr32(xf[c * FRAME + j], F.normshift[b] - 1), F.normg[b]);
+    }
+    wave_sync();
 }
 
 }  // namespace ca

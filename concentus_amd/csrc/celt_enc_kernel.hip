@@ -12,7 +12,8 @@
 //                               wavefront tiled through LDS, 78.5 KB per workgroup, 2 wavefronts per CU.
 //                               (celt_stage_kernels.hip)
 //   celt_front2_kernel          in_ws, FrameMid -> MDCT, band energies, patch_transient_decision, normalised bands X
-//                               -> FrameMid. Wave per frame, 8.7 KB LDS per workgroup, 16 wavefronts per CU.
+//                               -> FrameMid. Wave per frame, both channels through every lane loop together, 9.3 KB LDS
+//                               per workgroup, 16 wavefronts per CU.
 //   celt_back_lane_kernel       FrameMid -> packet, length, final range; the rest of the stream state (TF, coarse/fine
 //                               energy, allocation, PVQ, range coder). Lane per frame, 64 frames per wavefront, 40.6 KB
 //                               LDS per 64-frame workgroup, one wavefront per SIMD = 4 per CU.
@@ -45,7 +46,8 @@ __global__ __launch_bounds__(64, 3) void celt_front1_kernel(opusgpu_celt_config 
     }
 }
 
-// (64, 4): the one-channel working set (8.7 KB of LDS) admits 18 wavefronts per CU; the register budget is set for 16
+// (64, 4): the register budget is set for 16 wavefronts per CU, and the working set has to admit as many (160 KB of LDS)
+static_assert(sizeof(Front2Lds) * 16 <= 160 * 1024, "celt_front2_kernel: 16 wavefronts per CU");
 __global__ __launch_bounds__(64, 4) void celt_front2_kernel(opusgpu_celt_config cfg, FrameMid *__restrict__ mid,
                                                             i32 *__restrict__ in_ws, int nframes)
 {
@@ -145,7 +147,7 @@ extern "C" int opusgpu_encode_batch_args(const opusgpu_celt_config *cfg, const i
     return OPUSGPU_OK;
 }
 
-// persistent grids sized to what a CU holds: 13.9 KB of LDS per workgroup (11) / 8.7 KB at <= 128 VGPRs (16)
+// persistent grids sized to what a CU holds: 13.9 KB of LDS per workgroup (11) / 9.3 KB at <= 128 VGPRs (16)
 enum { FRONT1_WAVES = 11, FRONT2_WAVES = 16 };
 
 extern "C" void opusgpu_launch_front1(const opusgpu_celt_config *cfg, void *states, void *mid, int32_t *in_ws, int n, hipStream_t s)

@@ -94,6 +94,24 @@ CA_DEV int fft_lane(int lane) { return lane; }
 CA_DEV int fft_lane(int lane) { asm volatile("" : "+v"(lane)); return lane; }
 #endif
 
+// Two transforms side by side (NCH == 2, the two channels of a frame): a stage walks ONE index space of NCH x CNT entries, so
+// the last trip of its lane loop is filled from both. Entry idx belongs to transform idx / CNT, whose scratch lies
+// FFT_CH_STRIDE points after the first one's; fft_split reduces idx to the entry inside its transform and returns that
+// offset (a select, not a branch). Inside a transform nothing changes: same butterflies, tables and addressing.
+enum { FFT_CH_STRIDE = 480 };
+template <int NCH, int CNT>
+CA_DEV int fft_split(int &idx)
+{
+    static_assert(NCH == 1 || NCH == 2, "one transform or a pair");
+    if constexpr (NCH == 1) {
+        return 0;
+    } else {
+        const int ch = idx >= CNT ? 1 : 0;
+        idx -= ch * CNT;
+        return ch * FFT_CH_STRIDE;
+    }
+}
+
 // ---- bank swizzle of the FFT scratch (long transforms) ---------------------------------------------------
 // Point e of a 480-point transform lives at x[fsw<0>(e)]. Laid out plainly, the butterfly strides of the first stages
 // (4, 8, 32 points x 8 bytes) and the bit-reversed scatter of the pre-rotation (fifteen consecutive inputs land 32 points
@@ -157,12 +175,13 @@ CA_DEV void st2(int2 *p, cpx a, cpx b)
 }
 
 // ---- butterfly stages: B blocks of NFFT points laid out back to back in x[] ----------------------
-template <int NFFT, int B>
+template <int NFFT, int B, int NCH = 1>
 CA_DEV void fft_radix4_first(int2 *x, int lane)     // kiss_fft.c:123-145, m == 1
 {
     constexpr int CNT = B * NFFT / 4;
-    for (int idx = lane; idx < CNT; idx += LANES) {
-        int2 *f = x + 4 * idx;
+    for (int idx0 = lane; idx0 < NCH * CNT; idx0 += LANES) {
+        int idx = idx0;
+        int2 *f = x + fft_split<NCH, CNT>(idx) + 4 * idx;
         cpx x0 = ld(f), x1 = ld(f + 1), x2 = ld(f + 2), x3 = ld(f + 3);
         cpx s0 = c_sub(x0, x2);
         x0 = c_add(x0, x2);
@@ -177,15 +196,17 @@ CA_DEV void fft_radix4_first(int2 *x, int lane)     // kiss_fft.c:123-145, m == 
     }
 }
 
-template <int NFFT, int B>
+template <int NFFT, int B, int NCH = 1>
 CA_DEV void fft_radix2_m4(int2 *x, int lane)        // kiss_fft.c:72-107, m == 4
 {
     // one lane per (group, k) pair: k selects which of the four fixed rotations applies
     constexpr int CNT = B * NFFT / 2;
     constexpr i32 TW = 23170;
-    for (int idx = lane; idx < CNT; idx += LANES) {
+    for (int idx0 = lane; idx0 < NCH * CNT; idx0 += LANES) {
+        int idx = idx0;
+        int2 *xc = x + fft_split<NCH, CNT>(idx);
         int g = idx >> 2, k = idx & 3;
-        int2 *f = x + 8 * g + k;
+        int2 *f = xc + 8 * g + k;
         cpx a = ld(f), b = ld(f + 4), t;
         if (k == 0) {
             t = b;
@@ -207,13 +228,15 @@ CA_DEV void fft_radix2_m4(int2 *x, int lane)        // kiss_fft.c:72-107, m == 4
 // The first two stages of the 480-point transform -- radix 4 at m == 1 (kiss_fft.c:123-145) and radix 2 at m == 4
 // (:72-107) -- on eight consecutive points held by ONE lane: four 16-byte loads, twelve butterflies in registers, four
 // 16-byte stores; 60 lanes, one LDS round trip instead of two (and no 4- and 8-point strides across lanes).
-template <int SHIFT>
-CA_DEV void fft_first8(int2 *x, int lane)
+template <int SHIFT, int NCH = 1>
+CA_DEV void fft_first8(int2 *xb, int lane)
 {
     constexpr int NFFT = 480 >> SHIFT;
     constexpr i32 TW = 23170;
     lane = fft_lane(lane);
-    for (int g = lane; g < NFFT / 8; g += LANES) {
+    for (int g0 = lane; g0 < NCH * (NFFT / 8); g0 += LANES) {
+        int g = g0;
+        int2 *x = xb + fft_split<NCH, NFFT / 8>(g);
         cpx v[8];
         const int A = fsw<SHIFT>(8 * g);                                // the four pairs of a lane: fsw(8 g + 2 q) = fsw(8 g) ^ 2 q
 #pragma unroll
@@ -252,8 +275,8 @@ CA_DEV void fft_first8(int2 *x, int lane)
     }
 }
 
-template <int NFFT, int B, int M>
-CA_DEV void fft_radix4(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:146-176
+template <int NFFT, int B, int M, int NCH = 1>
+CA_DEV void fft_radix4(int2 *xb, const u32 *tw, int lane)   // kiss_fft.c:146-176
 {
     constexpr int G = NFFT / (4 * M);
     constexpr int TWS = G * (480 / NFFT);
@@ -261,7 +284,9 @@ CA_DEV void fft_radix4(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:146-176
     constexpr int SW = (NFFT == 480 && B == 1) ? 0 : 1;                 // layout: swizzled for the long transform only
     lane = fft_lane(lane);
     CA_FFT_ROLLED
-    for (int idx = lane; idx < CNT; idx += LANES) {
+    for (int idx0 = lane; idx0 < NCH * CNT; idx0 += LANES) {
+        int idx = idx0;
+        int2 *x = xb + fft_split<NCH, CNT>(idx);
         int blk = idx / (G * M), r = idx % (G * M);
         int g = r / M, j = r % M;
         const int e = blk * NFFT + g * 4 * M + j;
@@ -283,8 +308,8 @@ CA_DEV void fft_radix4(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:146-176
     }
 }
 
-template <int NFFT, int B, int M>
-CA_DEV void fft_radix3(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:185-241
+template <int NFFT, int B, int M, int NCH = 1>
+CA_DEV void fft_radix3(int2 *xb, const u32 *tw, int lane)   // kiss_fft.c:185-241
 {
     constexpr int G = NFFT / (3 * M);
     constexpr int TWS = G * (480 / NFFT);
@@ -293,7 +318,9 @@ CA_DEV void fft_radix3(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:185-241
     constexpr i32 EPI3 = -28378;
     lane = fft_lane(lane);
     CA_FFT_ROLLED
-    for (int idx = lane; idx < CNT; idx += LANES) {
+    for (int idx0 = lane; idx0 < NCH * CNT; idx0 += LANES) {
+        int idx = idx0;
+        int2 *x = xb + fft_split<NCH, CNT>(idx);
         int blk = idx / (G * M), r = idx % (G * M);
         int g = r / M, j = r % M;
         const int e = blk * NFFT + g * 3 * M + j;
@@ -314,8 +341,8 @@ CA_DEV void fft_radix3(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:185-241
     }
 }
 
-template <int NFFT, int B, int M>
-CA_DEV void fft_radix5(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:245-322
+template <int NFFT, int B, int M, int NCH = 1>
+CA_DEV void fft_radix5(int2 *xb, const u32 *tw, int lane)   // kiss_fft.c:245-322
 {
     constexpr int G = NFFT / (5 * M);
     constexpr int TWS = G * (480 / NFFT);
@@ -324,7 +351,9 @@ CA_DEV void fft_radix5(int2 *x, const u32 *tw, int lane)   // kiss_fft.c:245-322
     constexpr i32 YAR = 10126, YAI = -31164, YBR = -26510, YBI = -19261;
     lane = fft_lane(lane);
     CA_FFT_ROLLED
-    for (int idx = lane; idx < CNT; idx += LANES) {
+    for (int idx0 = lane; idx0 < NCH * CNT; idx0 += LANES) {
+        int idx = idx0;
+        int2 *x = xb + fft_split<NCH, CNT>(idx);
         int blk = idx / (G * M), r = idx % (G * M);
         int g = r / M, u = r % M;
         const int e = blk * NFFT + g * 5 * M + u;
@@ -362,36 +391,37 @@ template <int SHIFT, int B> CA_DEV cpx fft_get(const int2 *x, int e) { return ld
 
 // In-place FFT of B blocks of (480 >> SHIFT) bit-reversed points (opus_fft_impl, kiss_fft.c:532-578); the points are
 // addressed through fft_put / fft_get.
-template <int SHIFT, int B>
+// NCH == 2: the same on two scratch buffers FFT_CH_STRIDE points apart, every stage over both (fft_split).
+template <int SHIFT, int B, int NCH = 1>
 CA_DEV void fft_wave(int2 *x, const u32 *tw, int lane)
 {
     constexpr int NFFT = 480 >> SHIFT;
     if constexpr (SHIFT == 0 && B == 1) {
         // swizzled layout (fsw<0>): points written by fft_put<0, 1> / the MDCT pre-rotations, read back with fft_get<0, 1>
-        fft_first8<0>(x, lane);                 wave_sync();
-        fft_radix4<NFFT, B, 8>(x, tw, lane);    wave_sync();
-        fft_radix3<NFFT, B, 32>(x, tw, lane);   wave_sync();
-        fft_radix5<NFFT, B, 96>(x, tw, lane);   wave_sync();
+        fft_first8<0, NCH>(x, lane);                 wave_sync();
+        fft_radix4<NFFT, B, 8, NCH>(x, tw, lane);    wave_sync();
+        fft_radix3<NFFT, B, 32, NCH>(x, tw, lane);   wave_sync();
+        fft_radix5<NFFT, B, 96, NCH>(x, tw, lane);   wave_sync();
         return;
     }
-    fft_radix4_first<NFFT, B>(x, lane);
+    fft_radix4_first<NFFT, B, NCH>(x, lane);
     wave_sync();
     if constexpr (SHIFT == 0) {
-        fft_radix2_m4<NFFT, B>(x, lane);        wave_sync();
-        fft_radix4<NFFT, B, 8>(x, tw, lane);    wave_sync();
-        fft_radix3<NFFT, B, 32>(x, tw, lane);   wave_sync();
-        fft_radix5<NFFT, B, 96>(x, tw, lane);   wave_sync();
+        fft_radix2_m4<NFFT, B, NCH>(x, lane);        wave_sync();
+        fft_radix4<NFFT, B, 8, NCH>(x, tw, lane);    wave_sync();
+        fft_radix3<NFFT, B, 32, NCH>(x, tw, lane);   wave_sync();
+        fft_radix5<NFFT, B, 96, NCH>(x, tw, lane);   wave_sync();
     } else if constexpr (SHIFT == 1) {
-        fft_radix4<NFFT, B, 4>(x, tw, lane);    wave_sync();
-        fft_radix3<NFFT, B, 16>(x, tw, lane);   wave_sync();
-        fft_radix5<NFFT, B, 48>(x, tw, lane);   wave_sync();
+        fft_radix4<NFFT, B, 4, NCH>(x, tw, lane);    wave_sync();
+        fft_radix3<NFFT, B, 16, NCH>(x, tw, lane);   wave_sync();
+        fft_radix5<NFFT, B, 48, NCH>(x, tw, lane);   wave_sync();
     } else if constexpr (SHIFT == 2) {
-        fft_radix2_m4<NFFT, B>(x, lane);        wave_sync();
-        fft_radix3<NFFT, B, 8>(x, tw, lane);    wave_sync();
-        fft_radix5<NFFT, B, 24>(x, tw, lane);   wave_sync();
+        fft_radix2_m4<NFFT, B, NCH>(x, lane);        wave_sync();
+        fft_radix3<NFFT, B, 8, NCH>(x, tw, lane);    wave_sync();
+        fft_radix5<NFFT, B, 24, NCH>(x, tw, lane);   wave_sync();
     } else {
-        fft_radix3<NFFT, B, 4>(x, tw, lane);    wave_sync();
-        fft_radix5<NFFT, B, 12>(x, tw, lane);   wave_sync();
+        fft_radix3<NFFT, B, 4, NCH>(x, tw, lane);    wave_sync();
+        fft_radix5<NFFT, B, 12, NCH>(x, tw, lane);   wave_sync();
     }
 }
 
@@ -468,6 +498,113 @@ CA_DEV void mdct_forward_wave(const i32 *sin, int2 *f2, i32 *dst, int dstride, c
         dst[((N2 - 1 - 2 * i) * B + blk) * dstride] = add32(CA_SMUL(f.r, t1), CA_SMUL(f.i, t0));
     }
     wave_sync();
+}
+
+// Forward MDCT of BOTH channels of a frame, in place (the frame kernel's second front stage). sin: channel c's time signal
+// at sin + c * sin_stride. f2: two scratch buffers of FFT_CH_STRIDE points, one per channel, and nothing else -- coefficient k
+// of block b of channel c ends up in channel c's OWN scratch buffer viewed as i32[960], at word k * B + b (the layout
+// mdct_forward_wave writes with dstride 1). Fold + pre-rotation and every butterfly stage walk one index space over the two
+// channels.
+// The post-rotation turns FFT output i into coefficients 2 i and N2 - 1 - 2 i, which lie in the storage of OTHER outputs, so
+// it works on closed sets: outputs whose coefficients fill exactly the words the set occupies. The lanes rotate a set into
+// registers, and only when all of them have read does anyone store.
+//   long transform: the swizzle permutes inside aligned blocks of 32 points, so output i sits in block i >> 5; its
+//     coefficients go to words 2 i (block i >> 5) and 959 - 2 i (point 479 - i, block 14 - (i >> 5)). Blocks g and 14 - g of
+//     one channel are a closed set of 64 outputs -- one per lane -- and the two middle blocks (g = 7) of the two channels
+//     share a trip: 15 trips for the 960 outputs of a frame, two words held per lane.
+//   short blocks: coefficient k of block b goes to word 8 k + b, an 8 x 60 transpose with no small closed sets; a whole
+//     channel is the set (8 outputs per lane, 16 words held), one channel after the other.
+#if defined(CA_HOST_EMU)
+#define CA_POST_UNROLL
+#else
+#define CA_POST_UNROLL _Pragma("unroll")
+#endif
+template <int SHIFT, int B>
+CA_DEV void mdct_forward_wave2(const i32 *sin, int sin_stride, int2 *f2, const MdctTab &T, int lane)
+{
+    const u32 *trig = T.trig;
+    const i16 *bitrev = T.bitrev;
+    constexpr int NCH = 2;
+    constexpr int N2 = 960 >> SHIFT, N4 = N2 / 2, NFFT = N4;
+    static_assert(B * N4 == FFT_CH_STRIDE, "a whole frame per channel");
+    if constexpr (SHIFT == 0 && B == 1) {
+        if (lane < FFT_PAIR_STEP) {
+            CA_FFT_ROLLED
+            for (int n0 = 0; n0 < NCH * FFT_PAIRS; n0 += FFT_PAIR_STEP) {       // a trip lies in one channel (whole trips per channel)
+                const int ch = n0 >= FFT_PAIRS ? 1 : 0;
+                const i32 *in = sin + ch * sin_stride;
+                const int i = fft_pair_input(n0 - ch * FFT_PAIRS + lane);
+                const cpx a = mdct_fwd_pre<SHIFT>(in, i, T), b = mdct_fwd_pre<SHIFT>(in, i + 120, T);
+                st2(f2 + ch * FFT_CH_STRIDE + T.bitrev_sw[i], a, b);
+            }
+        }
+    } else {
+        for (int idx0 = lane; idx0 < NCH * B * N4; idx0 += LANES) {
+            int idx = idx0;
+            const int off = fft_split<NCH, B * N4>(idx);
+            const i32 *in = sin + (off / FFT_CH_STRIDE) * sin_stride;
+            int blk = idx / N4, i = idx % N4;
+            fft_put<SHIFT, B>(f2 + off, blk * NFFT + bitrev[i], mdct_fwd_pre<SHIFT>(in + blk * N2, i, T));
+        }
+    }
+    wave_sync();
+    fft_wave<SHIFT, B, NCH>(f2, T.tw, lane);
+    auto rotate = [&](const int2 *x, int e, int i, i32 &ya, i32 &yb) {          // mdct.c:237-257, output i of a block at point e
+        cpx f = fft_get<SHIFT, B>(x, e);
+        u32 tt = trig[i];
+        i32 t0 = lo16(tt), t1 = hi16(tt);
+        ya = sub32(CA_SMUL(f.i, t1), CA_SMUL(f.r, t0));
+        yb = add32(CA_SMUL(f.r, t1), CA_SMUL(f.i, t0));
+    };
+    if constexpr (SHIFT == 0 && B == 1) {
+        constexpr int SET = 64, PER = SET / LANES, NBLK = NFFT / 32, MID = NBLK / 2;         // 15 blocks, the middle one alone
+        static_assert(SET % LANES == 0 && NBLK == 2 * MID + 1, "block pairs g, 14 - g around a middle block");
+        CA_FFT_ROLLED
+        for (int t = 0; t < NCH * MID + 1; t++) {
+            // trips 0..6: channel 0, blocks t and 14 - t; 7..13: channel 1; 14: block 7 of channel 0 | block 7 of channel 1
+            const int last = t == NCH * MID, tc = t >= MID ? 1 : 0, g = last ? MID : t - tc * MID;
+            i32 ya[PER], yb[PER];
+            CA_POST_UNROLL
+            for (int u = 0; u < PER; u++) {
+                const int m = lane + u * LANES, hi = m >> 5;
+                const int ch = last ? hi : tc, i = 32 * (hi && !last ? NBLK - 1 - g : g) + (m & 31);
+                rotate(f2 + ch * FFT_CH_STRIDE, i, i, ya[u], yb[u]);
+            }
+            wave_sync();
+            CA_POST_UNROLL
+            for (int u = 0; u < PER; u++) {
+                const int m = lane + u * LANES, hi = m >> 5;
+                const int ch = last ? hi : tc, i = 32 * (hi && !last ? NBLK - 1 - g : g) + (m & 31);
+                i32 *dst = reinterpret_cast<i32 *>(f2 + ch * FFT_CH_STRIDE);
+                dst[2 * i] = ya[u];
+                dst[N2 - 1 - 2 * i] = yb[u];
+            }
+            wave_sync();
+        }
+    } else {
+        constexpr int PER = (B * N4 + LANES - 1) / LANES;
+        CA_FFT_ROLLED
+        for (int ch = 0; ch < NCH; ch++) {
+            int2 *x = f2 + ch * FFT_CH_STRIDE;
+            i32 ya[PER], yb[PER];
+            CA_POST_UNROLL
+            for (int u = 0; u < PER; u++) {
+                const int idx = lane + u * LANES;
+                if (idx < B * N4) rotate(x, idx, idx % N4, ya[u], yb[u]);
+            }
+            wave_sync();
+            CA_POST_UNROLL
+            for (int u = 0; u < PER; u++) {
+                const int idx = lane + u * LANES, blk = idx / N4, i = idx % N4;
+                if (idx < B * N4) {
+                    i32 *dst = reinterpret_cast<i32 *>(x);
+                    dst[(2 * i) * B + blk] = ya[u];
+                    dst[(N2 - 1 - 2 * i) * B + blk] = yb[u];
+                }
+            }
+            wave_sync();
+        }
+    }
 }
 
 // Inverse MDCT of B blocks. Coefficient k of block b is src[(k*B + b) * sstride]; block b produces
